@@ -2,6 +2,13 @@
 """Throughput of the heatmaps -> 3-D joints hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config NAME] [--backbone]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (frames/s, ms_per_step, host submit
+times); nothing else.  ``--full`` adds everything else the benchmark measures, after the timed steps: the serial
+rate, the long run, the per-class kernel timers and the roofline, the other configs / launch paths / end-to-end
+legs, the CPU baseline and the float parity against the reference fixtures (the ``--no-*`` options switch single
+parts of it off again).  ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy``.
 
 A step = one pass of the whole hot path (staging, HDN, JLN, fusion) over one batch of B
 synthetic frames per GPU: Panoptic shape set (5 views, 15 joints, 240x128 heatmaps, 80x80x20
@@ -82,6 +89,13 @@ def parse_args(argv=None):
                          "images per frame and runs the bf16 Pose-ResNet-50 backbone in front of the voxel path")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step from a captured hipGraph (per-kernel event timing is then unavailable)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float32; the inputs are seeded, so two builds can be compared output for output)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements: serial rate, long run, per-class "
+                         "kernel timers and roofline, other configs and launch paths, end to end, CPU baseline, float "
+                         "parity against the reference fixtures (a plain run does none of them)")
     return ap.parse_args(argv)
 
 
@@ -298,7 +312,7 @@ class Workload:
         # batches in flight: FV.PipelinedForward = one replica (scratch buffers) + one HIP stream each
         self.pipe = (FV.PipelinedForward(self.model, depth=self.nstreams, streams=stream_pool(dev, self.nstreams))
                      if self.nstreams > 1 else None)
-        self.bb = self.views_all = self.graphed = None
+        self.bb = self.views_all = self.graphed = self.last = None
         if backbone:
             from faster_voxelpose_amd.core import config as CFG
             from faster_voxelpose_amd.models import resnet as RN
@@ -315,14 +329,18 @@ class Workload:
             kw = dict(backbone=self.bb, views=self.views_all[i % len(self.views_all)])
         else:
             kw = dict(input_heatmaps=self.heats[i % self.nin])
+        # self.last: the forward's outputs of the latest step (fused, plane poses, centres, heatmaps, None), for
+        # --dump-outputs; valid until the next step is submitted
         if self.graphed is not None:
             # the graph's static output is overwritten by the next replay: hand the gather a private copy,
             # ordered behind this replay on the current stream (ResultGatherer waits for that stream)
-            return self.gatherer.gather(self.graphed(self.heats[i % self.nin])[0].clone())
+            self.last = self.graphed(self.heats[i % self.nin])
+            return self.gatherer.gather(self.last[0].clone())
         if self.pipe is not None and pipelined:
-            (fused, _, _, _, _), ev = self.pipe.submit(meta=self.meta, cameras=self.cams, resize_transform=self.rt, **kw)
-            return self.gatherer.gather(fused, ev)
-        fused = self.model(meta=self.meta, cameras=self.cams, resize_transform=self.rt, **kw)[0]
+            self.last, ev = self.pipe.submit(meta=self.meta, cameras=self.cams, resize_transform=self.rt, **kw)
+            return self.gatherer.gather(self.last[0], ev)
+        self.last = self.model(meta=self.meta, cameras=self.cams, resize_transform=self.rt, **kw)
+        fused = self.last[0]
         ev = torch.cuda.Event()
         ev.record()
         return self.gatherer.gather(fused, ev)
@@ -405,6 +423,38 @@ def serial_rate(wl, world, steps=5):
             wl.step(i, pipelined=False)
         wl.sync()
     return steps * wl.B * world / (time.perf_counter() - ts)
+
+
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20            # elements kept of an array larger than 16 MB (fixed seeded positions)
+
+
+def dump_outputs(dirname, out, wl):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy in float32.  fused_poses = what the step
+    returns (every rank's frames, gathered); plane_poses, proposal_centers = the rest of this rank's forward outputs;
+    with --backbone also the heatmaps the backbone computed, as input_heatmaps_sample (the values at DUMP_SAMPLE fixed
+    positions of the flattened tensor, drawn with seed 0: the whole tensor is larger than the budget).  Call it after
+    the timed steps and before anything else runs on the workload.  Returns the names written."""
+    import numpy as np
+    arrays = {"fused_poses": out}
+    if getattr(wl, "last", None) is not None:
+        arrays["plane_poses"], arrays["proposal_centers"] = wl.last[1], wl.last[2]
+        if wl.bb is not None:
+            arrays["input_heatmaps"] = wl.last[3]
+    os.makedirs(dirname, exist_ok=True)
+    names, total = [], 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        if a.nbytes > 16 << 20:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a, name = a.reshape(-1)[pos], name + "_sample"
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        names.append(name)
+    return names
 
 
 def secondary_leg(config, B, streams, steps, warmup, dev, backbone=False, serial=True):
@@ -525,6 +575,10 @@ def main():
     # FVP_GATHER_ISSUE=stream (diagnostics): the pre-round-6 GPU-side event wait instead of the host-issued gather
     gatherer = D.ResultGatherer(world, device=dev, always=force_dist, issue=os.environ.get("FVP_GATHER_ISSUE", "host"))
     lib = capi = None
+    if not args.full:
+        # a plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs,
+        # the result line
+        args.no_prof = args.no_cpu_baseline = args.no_mpjpe = args.no_extra = True
     if STUB:
         wl = StubWorkload(B, rank, gatherer)
         args.no_prof = args.no_cpu_baseline = args.no_mpjpe = args.no_extra = True
@@ -543,6 +597,8 @@ def main():
         gatherer.synchronize()
         dist.barrier()
     dt, out = timed_region(wl, args.steps, args.warmup, dist_on, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, wl)
     headline_host = {"submit_ms_per_step": HOST_TIMES.get("submit_ms_per_step"), "drain_ms": HOST_TIMES.get("drain_ms"),
                      "backpressure_wait_ms_per_step": HOST_TIMES.get("backpressure_wait_ms_per_step"),
                      "what": "host time to enqueue one step of the timed region (Python + ctypes launches); time the host was "
@@ -554,7 +610,7 @@ def main():
 
     # transparency: the strictly serial rate (one batch at a time on the current stream), 5 steps
     serial_fps = None
-    if not STUB and nstreams > 1 and not args.graph:
+    if args.full and not STUB and nstreams > 1 and not args.graph:
         serial_fps = serial_rate(wl, world)
     # secondary long run of the same step (>= 200 steady-state iterations)
     value_long = None
@@ -695,6 +751,7 @@ def main():
         line = {
             "metric": "frames/sec at 5-view 80x80x20 voxel (heatmaps -> 3D joints); MPJPE vs ref (mm) in mpjpe_vs_ref_mm",
             "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if not args.backbone else "bf16 backbone + f32 voxel path", "data": "synthetic",
             "config": {"workload": ("stub step (FVP_BENCH_STUB=1): launcher / timing protocol check, no GPU" if STUB else

@@ -1,8 +1,12 @@
 """bench.py pieces that can be checked without a GPU: the PMC-traffic gate (a traffic figure
-from another workload or another kernel variant must not reach the bench line) and the argument surface."""
+from another workload or another kernel variant must not reach the bench line), the argument surface, and the plain run
+with --dump-outputs on the CPU stand-in step."""
 import json
 import os
+import subprocess
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,3 +50,30 @@ def test_argument_surface():
     a = bench.parse_args(["--gpus", "8", "--config", "panoptic128", "--batch", "1", "--steps", "5", "--warmup", "2"])
     assert (a.gpus, a.config, a.batch, a.steps, a.warmup) == (8, "panoptic128", 1, 5, 2)
     assert bench.parse_args(["--backbone"]).backbone
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) on the CPU stand-in step (FVP_BENCH_STUB=1): exactly --steps timed steps behind
+    ms_per_step, none of the secondary measurements, and --dump-outputs writes the last step's result, the same
+    bits from run to run."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["FVP_BENCH_STUB"] = "1"
+    dumped = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--batch", "3",
+                            "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["full"] is False and d["ms_per_step"] > 0
+        assert abs(d["value"] - 3 * 5 / (d["ms_per_step"] * 5e-3)) < 1e-6 * d["value"]
+        assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["cpu_baseline"] is None and d["mpjpe_vs_ref_mm"] is None and d["kernels"] == {}
+        assert d["value_long"] is None and d["other_configs"] is None
+        assert sorted(os.listdir(tmp_path / run)) == ["fused_poses.npy"]
+        dumped.append(np.load(tmp_path / run / "fused_poses.npy"))
+    assert dumped[0].dtype == np.float32 and dumped[0].shape == (3, 10, 15, 5)
+    assert np.array_equal(dumped[0], dumped[1])
+    assert np.array_equal(dumped[0][:, 0, 0, 0], np.arange(3, dtype=np.float32))     # the stand-in step's frame ids

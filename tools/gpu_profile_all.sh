@@ -14,14 +14,14 @@ echo "== pytest -m gpu"; rm -f "$out/parity_report.jsonl"
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider > "$out/pytest_gpu_${tag}.log" 2>&1; echo "pytest rc=$?"; tail -3 "$out/pytest_gpu_${tag}.log"
 cp "$out/parity_report.jsonl" "$dst/${tag}_parity_report.jsonl" 2>/dev/null
 echo "== bench"
-timeout 600 python bench.py --steps 20 --warmup 3 > "$dst/${tag}_bench_b8.json" 2> "$out/bench_${tag}.err"; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 3 > "$dst/${tag}_bench_b8.json" 2> "$out/bench_${tag}.err"; echo "bench rc=$?"
 for spec in "1 1" "1 4" "2 4" "8 1" "8 2" "8 3" "16 4" "32 4"; do
   set -- $spec
-  timeout 300 python bench.py --steps 10 --warmup 3 --batch $1 --streams $2 --no-cpu-baseline --no-extra > "$dst/${tag}_bench_b$1_s$2.json" 2>> "$out/bench_${tag}.err"
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --batch $1 --streams $2 --no-cpu-baseline --no-extra > "$dst/${tag}_bench_b$1_s$2.json" 2>> "$out/bench_${tag}.err"
 done
 timeout 300 python tools/bench_backbone.py --images 40 --iters 3 --per-op > "$dst/${tag}_backbone_per_op.log" 2>&1
 for st in 1 2 3; do
-  timeout 300 python bench.py --backbone --steps 8 --warmup 2 --streams $st --no-cpu-baseline --no-extra > "$dst/${tag}_bench_e2e_b8_s$st.json" 2>> "$out/bench_${tag}.err"
+  timeout 300 python bench.py --full --backbone --steps 8 --warmup 2 --streams $st --no-cpu-baseline --no-extra > "$dst/${tag}_bench_e2e_b8_s$st.json" 2>> "$out/bench_${tag}.err"
 done
 timeout 300 python tools/bench_conv.py --net conv_net --frames 8 --iters 10 > "$dst/${tag}_conv_per_op_p2pnet_b8.log" 2>&1
 timeout 300 python tools/bench_conv.py --net center_net --frames 8 --iters 10 > "$dst/${tag}_conv_per_op_centernet_b8.log" 2>&1

@@ -4,7 +4,7 @@ root="${GRAFT_REPO_ROOT:-$(pwd)}"; out="$root/gpurun_out"; mkdir -p "$out"; cd "
 tag="${1:-r06a}"
 rm -f "$out/parity_report.jsonl"
 timeout 1200 python -m pytest tests -m gpu -q -x -p no:cacheprovider > "$out/pytest_gpu_${tag}.log" 2>&1; echo "pytest rc=$?"; tail -5 "$out/pytest_gpu_${tag}.log"
-timeout 600 python bench.py --steps 20 --warmup 3 > "$out/bench_${tag}.json" 2> "$out/bench_${tag}.err"; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 3 > "$out/bench_${tag}.json" 2> "$out/bench_${tag}.err"; echo "bench rc=$?"
 python - "$out/bench_${tag}.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

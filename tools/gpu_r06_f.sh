@@ -3,7 +3,7 @@
 root="${GRAFT_REPO_ROOT:-$(pwd)}"; out="$root/gpurun_out"; mkdir -p "$out"; cd "$root"; export TMPDIR=/tmp
 rm -f "$out/parity_report.jsonl"
 timeout 1200 python -m pytest tests -m gpu -q -x -p no:cacheprovider 2>&1 | tail -4
-timeout 600 python bench.py --steps 20 --warmup 3 > "$out/bench_r06f.json" 2> "$out/bench_r06f.err"; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 20 --warmup 3 > "$out/bench_r06f.json" 2> "$out/bench_r06f.err"; echo "bench rc=$?"
 python - "$out/bench_r06f.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

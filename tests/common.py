@@ -238,28 +238,229 @@ def check_outputs(case, g, fused, planes, centers, engine, report=None):
     np.testing.assert_allclose(pl, g["plane_poses"], rtol=0, atol=tol)
 
 
-def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_valid=None):
+# NaN bit pattern of the poisoned buffers (run_custom_conv_stack(poison=True)): a quiet NaN no float operation produces
+POISON_BITS = 0x7FA5A5A5
+POISON_GUARD = 4096            # floats of guard region before and after every poisoned buffer
+
+
+def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_valid=None, valid_div=1, poison=False, eps=1e-5,
+                          info=None):
     """Run a hand-made ``netspec.StackSpec`` (finalized) through fvp_pack_conv + fvp_conv_stack_run.
-    ``weights``: {key + '.weight' / '.bias': tensor}; ``x``: [planes, C, H, W].  Returns every activation buffer."""
+    ``weights``: {key + '.weight' / '.bias': tensor}, and for a conv with a BN key {bn + '.weight' / '.bias' /
+    '.running_mean' / '.running_var'}; ``x``: [planes, C, H, W].  Returns every activation buffer.
+    ``info`` (a dict, optional) receives the packed parameter blob (``info['blob']``: bias | scale | shift at each op's e_off).
+    ``poison=True``: every buffer, the input included, is carved out of an allocation with POISON_GUARD floats of guard
+    before and after it; guards and outputs are pre-filled with POISON_BITS.  Returns (buffers, check); check() asserts that
+    every guard is bit-identical (else the stack wrote out of bounds) and that every output element of a valid plane
+    (plane_valid[n // valid_div] != 0) is finite (a NaN there was read from memory the zero padding should have masked,
+    or is an element nobody wrote).  On the CPU emulation (tests/hipemu) the guards are also read fences: check() asserts
+    that no emulated buffer load read them, even a value the kernel then discarded."""
     import ctypes as C
 
     from faster_voxelpose_amd import _capi as capi
     blob = torch.zeros(max(spec.nparams, 4), device=device)
     s = stream
+    keep = []
     for key, bn, transposed, oi in spec.param_keys:
-        assert bn is None
         w = weights[key + ".weight"].to(device).contiguous()
         b = weights[key + ".bias"].to(device).contiguous()
-        capi.check(lib, lib.fvp_pack_conv(C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), None, None, None, None, 1e-5,
+        bnp = [None] * 4
+        if bn is not None:
+            bnt = [weights[bn + k].to(device=device, dtype=torch.float32).contiguous()
+                   for k in (".weight", ".bias", ".running_mean", ".running_var")]
+            keep += bnt
+            bnp = [C.c_void_p(t.data_ptr()) for t in bnt]
+        capi.check(lib, lib.fvp_pack_conv(C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), *bnp, eps,
                                           1 if transposed else 0, C.byref(spec.op_array[oi]), C.c_void_p(blob.data_ptr()), s),
                    "fvp_pack_conv")
     planes = x.shape[0]
-    bufs = [x.to(device).contiguous()] + [torch.empty((planes,) + tuple(b), device=device) for b in spec.bufs[1:]]
+    shapes = [(planes,) + tuple(b) for b in spec.bufs]
+    if not poison:
+        bufs = [x.to(device).contiguous()] + [torch.empty(sh, device=device) for sh in shapes[1:]]
+    else:
+        G = POISON_GUARD
+        flats, bufs = [], []
+        for i, sh in enumerate(shapes):
+            n = int(np.prod(sh))
+            f = torch.full((n + 2 * G,), POISON_BITS, dtype=torch.int32, device=device).view(torch.float32)
+            v = f[G:G + n].view(sh)
+            if i == 0:
+                v.copy_(x.to(device))
+            flats.append(f)
+            bufs.append(v)
+    fence = poison and device == "cpu" and hasattr(lib, "hipemu_fence")
+    if fence:                     # the CPU emulation also counts reads of the guards (tests/hipemu: read fences)
+        lib.hipemu_fence.argtypes = [C.c_void_p, C.c_size_t]
+        lib.hipemu_fenced_reads.restype = C.c_long
+        lib.hipemu_fences_clear()
+        for f in flats:
+            n = f.numel() - 2 * G
+            lib.hipemu_fence(C.c_void_p(f.data_ptr()), 4 * G)
+            lib.hipemu_fence(C.c_void_p(f.data_ptr() + 4 * (G + n)), 4 * G)
     arr = (C.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
     pv = None if plane_valid is None else plane_valid.to(device=device, dtype=torch.uint8).contiguous()
     capi.check(lib, lib.fvp_conv_stack_run(spec.op_array, len(spec.ops), C.c_void_p(blob.data_ptr()), arr, len(bufs), planes,
-                                           None if pv is None else C.c_void_p(pv.data_ptr()), 1, s), "fvp_conv_stack_run")
-    return bufs
+                                           None if pv is None else C.c_void_p(pv.data_ptr()), valid_div, s), "fvp_conv_stack_run")
+    reads = 0
+    if fence:
+        reads = int(lib.hipemu_fenced_reads())
+        lib.hipemu_fences_clear()
+    if info is not None:
+        info["blob"] = blob
+    if not poison:
+        return bufs
+
+    def check():
+        # (on the device: the buffers of a 240-plane layer are gigabytes)
+        valid = torch.ones(planes, dtype=torch.bool)
+        if plane_valid is not None:
+            valid = plane_valid.cpu().bool()[torch.arange(planes) // valid_div]
+        valid = valid.to(device)
+        assert reads == 0, f"{reads} reads of guard words (memory the kernel's masking should have kept it from)"
+        for i, f in enumerate(flats):
+            bits = f.view(torch.int32)
+            n = bits.numel() - 2 * G
+            bad = int((bits[:G] != POISON_BITS).sum()) + int((bits[G + n:] != POISON_BITS).sum())
+            assert bad == 0, f"buffer {i}: {bad} guard words changed (out-of-bounds write)"
+            if i > 0:
+                nf = int((~torch.isfinite(bufs[i][valid])).sum())
+                assert nf == 0, f"buffer {i}: {nf} non-finite elements in valid planes (unwritten, or read unmasked memory)"
+    return bufs, check
+
+
+# ---- Winograd F(2x2,3x3) layer tests (tests/test_wino_*.py) ---------------------------------------------------------------
+# A-priori error bound of one k_conv_wino layer against its float64 evaluation, per output element:
+#
+#     |y - y64| <= gamma * ( |s| * (conv(|x|, |w|) + |b|) + |t| + |r| ),   gamma = WINO_K * eps32
+#
+# (s, t: the BN scale / shift the layer packed, b: bias, r: the residual; ReLU and max-pool are 1-Lipschitz, so the same
+# bound - max-pooled - covers the ReLU'd and the pooled outputs).  WINO_K counts the fp32 roundings on the longest path of one
+# output and scales them by the magnitude growth of the transforms:
+#   * outside the channel sum: input transform B^T d B 2 (row pass, column pass; every V is a +-1 combination), weight
+#     transform G g G^T 4 (two adds per pass, the halving is exact), output transform A^T M A 4 (two adds per pass), the
+#     epilogue 3 (acc + bias, the BN fma, + residual): WINO_ROUNDINGS = 13;
+#   * the channel sum: one fma per channel in one chain (v_mfma_f32_16x16x4_f32 accumulates 4 channels per instruction,
+#     chunk after chunk): at most WINO_CIN_MAX = 128 (the widest layer of P2PNet / CenterNet);
+#   * the standard bound of a length-n fp32 evaluation is n * eps32 relative to the same sum of magnitudes.  The Winograd
+#     form sums magnitudes of the transformed operands, |A^T| ( sum_ci |G g G^T| .* |B^T d B| ) |A|, which is a few times
+#     conv(|x|, |w|): every U = G g G^T entry mixes up to 9 taps with weights <= 1/4 .. 1, every V up to 4 inputs, and
+#     A^T sums 3 of the 16 products per output and pass.  For data with more than a handful of taps x channels per output the
+#     ratio concentrates near 2 .. 3; WINO_SPREAD = 4 covers it (pointwise it is unbounded - an output whose own taps see
+#     zeros while the rest of its 4x4 patch does not - which is why this is a bound for the random operands of these tests,
+#     not for every possible input).
+#   WINO_K = WINO_SPREAD * (WINO_ROUNDINGS + WINO_CIN_MAX) = 564.
+# Measured (worst error / bound over every case): see tests/test_wino_emu.py (emulator) and tests/test_wino_conv.py (MI355X);
+# both far below 1/2.  tests/test_wino_emu.py::test_wino_bound_rejects_mutated_references shows the bound is still sharp enough
+# to reject a dropped channel, a missing tap, a wrong halo, a wrong residual, a shifted BN block or a misplaced ReLU.
+WINO_ROUNDINGS = 13
+WINO_CIN_MAX = 128
+WINO_SPREAD = 4
+WINO_K = WINO_SPREAD * (WINO_ROUNDINGS + WINO_CIN_MAX)
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def wino_layer(cin, cout, hw, *, relu=True, res=False, res_after=False, bn=False, pool=False, seed=0):
+    """One 3x3 conv (+ BN, residual, ReLU, fused 2x2 max-pool) as a finalized ``netspec.StackSpec``.  The residual is the
+    input when cin == cout, else a 1x1 projection of the input earlier in the same stack (the product's res blocks);
+    ``pool`` adds spec.pool() on the conv output, which the interpreter fuses into the Winograd epilogue.
+    Returns (spec, weights, ids) with ids = {'out', 'res' (buffer id or None), 'pool' (or None), 'op' (the conv's op index)}."""
+    from faster_voxelpose_amd import netspec
+    h, w_ = (hw, hw) if isinstance(hw, int) else hw
+    spec = netspec.StackSpec(2, cin, (h, w_))
+    spec._conv_entries("c", cin, cout, 3)
+    if bn:
+        spec._bn_entries("n", cout)
+    rid = None
+    if res:
+        if cin == cout:
+            rid = 0
+        else:
+            spec._conv_entries("p", cin, cout, 1)
+            rid = spec.conv("p", None, 0, cout, 1, relu=False)
+    o = spec.conv("c", "n" if bn else None, 0, cout, 3, relu=relu, res=rid, res_after_relu=res_after)
+    op = len(spec.ops) - 1
+    pid = spec.pool(o) if pool else None
+    spec.outputs["out"] = o
+    spec.finalize()
+    g = torch.Generator().manual_seed(seed)
+    wt = {"c.weight": torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5, "c.bias": torch.randn(cout, generator=g) * 0.1}
+    if res and cin != cout:
+        wt["p.weight"] = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
+        wt["p.bias"] = torch.randn(cout, generator=g) * 0.1
+    if bn:
+        # scales of both signs and per-cout shifts that differ from one 32-cout block to the next
+        blk = (torch.arange(cout) // 32).float()
+        wt["n.weight"] = (0.5 + torch.rand(cout, generator=g)) * torch.where(torch.rand(cout, generator=g) < 0.3, -1.0, 1.0) * (1 + 0.25 * blk)
+        wt["n.bias"] = torch.randn(cout, generator=g) * 0.2 + 0.1 * blk
+        wt["n.running_mean"] = torch.randn(cout, generator=g) * 0.1 - 0.05 * blk
+        wt["n.running_var"] = 0.5 + torch.rand(cout, generator=g) + 0.1 * blk
+    return spec, wt, dict(out=o, res=rid, pool=pid, op=op)
+
+
+def wino_reference(weights, x, r, scale, shift, relu=True, res_after=False, pool=False):
+    """float64 evaluation of the layer and the magnitude term of the error bound (see WINO_K).  x [P, cin, H, W];
+    r: the residual buffer as the device holds it (or None); scale / shift: the packed per-cout BN vectors (float32 values,
+    as the kernel reads them).  Returns dict(y, mag[, p, pmag]) in float64."""
+    import torch.nn.functional as F
+    w = weights["c.weight"].double()
+    b = weights["c.bias"].double()
+    x = x.double()
+    s = scale.double().view(1, -1, 1, 1)
+    t = shift.double().view(1, -1, 1, 1)
+    z = F.conv2d(x, w, None, padding=1) + b.view(1, -1, 1, 1)
+    y = z * s + t
+    if r is not None and not res_after:
+        y = y + r.double()
+    if relu:
+        y = torch.relu(y)
+    if r is not None and res_after:
+        y = y + r.double()
+    mag = s.abs() * (F.conv2d(x.abs(), w.abs(), None, padding=1) + b.abs().view(1, -1, 1, 1)) + t.abs()
+    if r is not None:
+        mag = mag + r.double().abs()
+    out = dict(y=y, mag=mag)
+    if pool:
+        out["p"] = F.max_pool2d(y, 2)
+        out["pmag"] = F.max_pool2d(mag, 2)
+    return out
+
+
+def wino_ratio(y, y64, mag, gamma=None):
+    """max |y - y64| / (gamma * mag) (gamma defaults to WINO_K * eps32); > 1 = the bound is violated.  NaN counts as a violation."""
+    gamma = WINO_K * EPS32 if gamma is None else gamma
+    err = (y.double() - y64).abs()
+    if not torch.isfinite(err).all():
+        return float("inf")
+    return float((err / (gamma * mag + 1e-300)).max())
+
+
+def wino_packed_bn(spec, blob, op):
+    """(scale, shift) of op ``op`` as packed in the parameter blob (float32, on the CPU)."""
+    o = spec.op_array[op]
+    e = blob[o.e_off:o.e_off + 3 * o.coutp].cpu()
+    return e[o.coutp:o.coutp + o.cout], e[2 * o.coutp:2 * o.coutp + o.cout]
+
+
+def wino_prof_launches(lib, run):
+    """Winograd launches made by ``run()`` on the GPU: (FVP_K_CONV_WINO, FVP_K_CONV_WINO_SMALL) counts of the per-launch
+    profiler (fvp_prof_enable(2)); the profiler is reset and switched off again afterwards."""
+    import ctypes as C
+
+    from faster_voxelpose_amd import _capi as capi
+    lib.fvp_prof_reset()
+    lib.fvp_prof_enable(2)
+    try:
+        run()
+        torch.cuda.synchronize()
+        counts = []
+        for cls in (capi.K_CONV_WINO, capi.K_CONV_WINO_SMALL):
+            ms, n, fl = C.c_double(), C.c_int64(), C.c_double()
+            lib.fvp_prof_read(cls, C.byref(ms), C.byref(n), C.byref(fl))
+            counts.append(int(n.value))
+    finally:
+        lib.fvp_prof_enable(0)
+        lib.fvp_prof_reset()
+    return tuple(counts)
 
 
 def split_k_stack(cin, cmid, hw, seed=0):

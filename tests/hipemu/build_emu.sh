@@ -20,5 +20,5 @@ o="${here}/hipemu.emu.o"
 "$CXX" "${flags[@]}" -c "${here}/hipemu.cpp" -o "$o" &
 objs+=("$o")
 wait
-"$CXX" -shared -fPIC "${objs[@]}" -o "${here}/libfvp_emu.so" -lpthread
+"$CXX" -shared -fPIC "${objs[@]}" -o "${here}/libfvp_emu.so" -lpthread -ldl
 echo "built ${here}/libfvp_emu.so"

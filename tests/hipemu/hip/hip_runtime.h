@@ -65,6 +65,12 @@ void block_barrier();
 void wave_exchange(const uint32_t* mine, int n, uint32_t (*all)[4]);
 void wave_exchange_done();
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
+// launch log (tests only): the symbol of every launched kernel, read back through hipemu_launch_log()
+void log_launch(const void* kernel);
+// read fences (tests only, hipemu_fence): the emulated buffer loads count every dword they read inside a fenced range - a
+// read the kernel's masking should have kept out of memory, even when the value it brings is discarded
+extern int nfences;
+void fenced_read_check(const void* p);
 }  // namespace hipemu
 
 #define threadIdx (hipemu::cur->tid)
@@ -78,6 +84,7 @@ static inline void __syncthreads() { hipemu::block_barrier(); }
 template <typename... KArgs, typename... Args>
 static inline void hipLaunchKernelGGL(void (*k)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStream_t,
                                       Args... args) {
+  hipemu::log_launch(reinterpret_cast<const void*>(k));
   hipemu::launch(grid, block, shmem, [=]() { k(args...); });
 }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -234,7 +241,10 @@ static inline void asm_buffer_load_lds16(unsigned la, unsigned vo, const fvp_i32
   for (int d = 0; d < 4; ++d) {
     const unsigned long long off = (unsigned long long)vo + so + 4ull * d;
     float v = 0.0f;
-    if (off + 4 <= nrec) memcpy(&v, (const char*)base + off, 4);
+    if (off + 4 <= nrec) {
+      if (hipemu::nfences) hipemu::fenced_read_check((const char*)base + off);
+      memcpy(&v, (const char*)base + off, 4);
+    }
     memcpy(dst + 4 * d, &v, 4);
   }
 }
@@ -247,7 +257,10 @@ static inline fvp_f32x2 asm_buffer_load_f32x2(unsigned vo, const fvp_i32x4& rs, 
   float t[2] = {0.0f, 0.0f};
   const unsigned long long off = (unsigned long long)vo + so, nrec = (unsigned)rs[2];
   for (int d = 0; d < 2; ++d)
-    if (off + 4ull * d + 4 <= nrec) memcpy(&t[d], hipemu_rs_base(rs) + off + 4 * d, 4);
+    if (off + 4ull * d + 4 <= nrec) {
+      if (hipemu::nfences) hipemu::fenced_read_check(hipemu_rs_base(rs) + off + 4 * d);
+      memcpy(&t[d], hipemu_rs_base(rs) + off + 4 * d, 4);
+    }
   return fvp_f32x2{t[0], t[1]};
 }
 static inline void asm_buffer_store_f32x2(fvp_f32x2 v, unsigned vo, const fvp_i32x4& rs, unsigned so) {
@@ -269,7 +282,10 @@ static inline fvp_rsrc make_rsrc(const void* p, unsigned bytes) { return fvp_rsr
 static inline float buf_load_f32(fvp_rsrc r, unsigned vo, unsigned so) {
   const unsigned long long off = (unsigned long long)vo + so;
   float v = 0.0f;
-  if (off + 4 <= r.nrec) memcpy(&v, r.base + off, 4);
+  if (off + 4 <= r.nrec) {
+    if (hipemu::nfences) hipemu::fenced_read_check(r.base + off);
+    memcpy(&v, r.base + off, 4);
+  }
   return v;
 }
 static inline float2 buf_load_f32x2(fvp_rsrc r, unsigned vo, unsigned so) {

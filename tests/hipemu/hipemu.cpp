@@ -2,9 +2,12 @@
 // TEST INFRASTRUCTURE ONLY (see hip/hip_runtime.h in this directory).
 #include <hip/hip_runtime.h>
 
+#include <dlfcn.h>
 #include <sys/mman.h>
 
 #include <atomic>
+#include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -199,4 +202,50 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& bo
   }
 }
 
+// ---- launch log: one line per launch, the kernel's (mangled) symbol as the dynamic linker names it
+static std::mutex log_mu;
+static std::string log_text;
+
+void log_launch(const void* kernel) {
+  Dl_info info;
+  const char* name = (dladdr(kernel, &info) && info.dli_sname) ? info.dli_sname : "?";
+  std::lock_guard<std::mutex> lk(log_mu);
+  log_text += name;
+  log_text += '\n';
+}
+
+// ---- read fences: [begin, end) byte ranges, set between launches only
+int nfences = 0;
+static std::vector<std::pair<uintptr_t, uintptr_t>> fences;
+static std::atomic<long> fenced_reads{0};
+
+void fenced_read_check(const void* p) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  for (const auto& f : fences)
+    if (a + 4 > f.first && a < f.second) fenced_reads.fetch_add(1, std::memory_order_relaxed);
+}
+
 }  // namespace hipemu
+
+extern "C" void hipemu_fence(const void* p, size_t bytes) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  hipemu::fences.emplace_back(a, a + bytes);
+  hipemu::nfences = int(hipemu::fences.size());
+}
+// clears the fences and the count of fenced reads
+extern "C" void hipemu_fences_clear() {
+  hipemu::fences.clear();
+  hipemu::nfences = 0;
+  hipemu::fenced_reads = 0;
+}
+extern "C" long hipemu_fenced_reads() { return hipemu::fenced_reads.load(); }
+
+// the log since the last reset (valid until the next launch or reset: the caller copies it)
+extern "C" const char* hipemu_launch_log() {
+  std::lock_guard<std::mutex> lk(hipemu::log_mu);
+  return hipemu::log_text.c_str();
+}
+extern "C" void hipemu_launch_log_reset() {
+  std::lock_guard<std::mutex> lk(hipemu::log_mu);
+  hipemu::log_text.clear();
+}

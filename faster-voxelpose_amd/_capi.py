@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 8            # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 9            # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -22,6 +22,7 @@ K_PROJECT_WHOLE, K_PROJECT_TRIPLANE, K_CONV, K_SOFTARGMAX, K_OTHER, K_CONV_WINO,
 BB_CONV, BB_MAXPOOL, BB_DECONV = 0, 1, 2
 BB_OUT_HEAT = 8
 BB_STEM = 16
+INGEST_SWAP_RB, INGEST_GENERAL = 1, 2
 
 
 class FvpGeom(C.Structure):
@@ -73,6 +74,7 @@ SIGNATURES = {
     "fvp_pack_weightnet": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _P, _P],
     "fvp_fuse_poses": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "fvp_rasterise_heatmaps": [_P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _I, _P],
+    "fvp_ingest_frames": [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I, _I, _P, _P, _P],
     "fvp_bb_input": [_P, _P, _I, _I, _I, _I, _P],
     "fvp_bb_pack": [_P, _P, _P, _P, _P, _P, _F, C.POINTER(FvpBbOp), _P, _P, _P],
     "fvp_bb_run": [C.POINTER(FvpBbOp), _I, _P, _P, C.POINTER(_P), _I, _I, _P, _I, _P, _P],

@@ -9,7 +9,12 @@
 // arithmetic of the reference is float64 (numpy promotes the float32 arange against float64
 // scalars) and is kept in float64 here: integer truncations, floor division and the IEEE sqrt /
 // division are exact, so window positions are bit-identical; exp(double) is rounded to float32 once.
+//
+// Second input producer of this file: camera frames -> backbone input (k_ingest_*, fvp_ingest_frames below).
 #include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
 
 #include "fvp_common.h"
 
@@ -99,6 +104,89 @@ k_rasterise(const double* __restrict__ joints, const int* __restrict__ num_peopl
     }
 }
 
+
+// ---- camera frames -> backbone input ----------------------------------------------------------------------------------
+// uint8 HWC frames at the camera's resolution -> bilinear warp through a 2x3 matrix (destination pixel -> source pixel,
+// taps outside the frame are 0), channel swap, / 255, mean / std: the reference's preprocess.py warpAffine call and its
+// loader (JointsDataset.py:129-133, run/validate.py:44-52) in one pass, written as the stem's pixel-pair bf16 input
+// (k_bb_input's layout) and / or as the fp32 NCHW tensor a torch backbone reads.  Memory traffic only: one lane per
+// destination pixel PAIR, one 16-byte store.
+//
+// The arithmetic is fixed (include/fvp.h) and lives in ingest_pair(), which takes the source of a tap's byte as a
+// functor.  One form ships: k_ingest_gather reads the bytes from global memory (any matrix).  A second form that first
+// copied the source rectangle of a 128 x 4 destination tile into LDS with 16-byte loads (rows realigned by their byte
+// offset) computed the same bits but was not faster on the card - 257 us against 192 us for 40 frames 1080p -> 512x960,
+// 159 against 167 us at 512x960 -> 512x960 (profiles/ingest_kernel.txt) - and was dropped; FVP_INGEST_GENERAL is
+// accepted and changes nothing.  This TU is compiled with -ffp-contract=off: every * + - / below is rounded on its own.
+struct IngestPrm {
+  float inv[6], mean[3], stdv[3];
+};
+struct alignas(16) IngestB16 { uint32_t w[4]; };            // one 16-byte store
+
+__device__ __forceinline__ uint16_t ingest_f2bf(float f) {   // round to nearest even: f2bf of fvp_backbone.hip
+  uint32_t u = uint32_t(__float_as_int(f));
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return uint16_t(u >> 16);
+}
+
+__device__ __forceinline__ float ingest_coord(float a, float b, float c, int x, int y) {
+  return a * float(x) + b * float(y) + c;
+}
+
+// floor() of a source coordinate as an int; anything that cannot have a tap inside [0, n) becomes -2 (both taps outside)
+__device__ __forceinline__ int ingest_cell(float fl, int n) { return (fl >= -1.0f && fl < float(n)) ? int(fl) : -2; }
+
+// Destination pixels (2 * xp, y) and (2 * xp + 1, y) of image n.  tap(yy, xx, c) = source byte as float, both
+// coordinates already inside the frame.
+template <class Tap>
+__device__ __forceinline__ void ingest_pair(const IngestPrm& p, int Hs, int Ws, int H, int W, int swap, int n, int y, int xp,
+                                            uint16_t* __restrict__ nhwc8, float* __restrict__ nchw, Tap tap) {
+  uint16_t v16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const long hw = long(H) * W;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int x = 2 * xp + e;
+    const float sx = ingest_coord(p.inv[0], p.inv[1], p.inv[2], x, y);
+    const float sy = ingest_coord(p.inv[3], p.inv[4], p.inv[5], x, y);
+    const float flx = floorf(sx), fly = floorf(sy);
+    const float fx = sx - flx, fy = sy - fly;
+    const int x0 = ingest_cell(flx, Ws), y0 = ingest_cell(fly, Hs);
+    const bool xa = x0 >= 0, xb = x0 + 1 >= 0 && x0 + 1 < Ws, ya = y0 >= 0, yb = y0 + 1 >= 0 && y0 + 1 < Hs;
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int sc = swap ? 2 - c : c;
+      const float p00 = ya && xa ? tap(y0, x0, sc) : 0.0f, p01 = ya && xb ? tap(y0, x0 + 1, sc) : 0.0f;
+      const float p10 = yb && xa ? tap(y0 + 1, x0, sc) : 0.0f, p11 = yb && xb ? tap(y0 + 1, x0 + 1, sc) : 0.0f;
+      const float v = gy * (gx * p00 + fx * p01) + fy * (gx * p10 + fx * p11);
+      const float o = __fdiv_rn(__fdiv_rn(v, 255.0f) - p.mean[c], p.stdv[c]);
+      v16[4 * e + c] = ingest_f2bf(o);
+      if (nchw) nchw[(long(n) * 3 + c) * hw + long(y) * W + x] = o;
+    }
+  }
+  if (nhwc8) {
+    IngestB16 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o.w[e] = uint32_t(v16[2 * e]) | (uint32_t(v16[2 * e + 1]) << 16);
+    *reinterpret_cast<IngestB16*>(nhwc8 + ((long(n) * H + y) * (W / 2) + xp) * 8) = o;
+  }
+}
+
+// Any matrix, 12 byte loads per pixel through L1.
+__global__ void __launch_bounds__(256)
+k_ingest_gather(const uint8_t* __restrict__ frames, int N, int Hs, int Ws, IngestPrm p, int H, int W, int swap,
+                uint16_t* __restrict__ nhwc8, float* __restrict__ nchw) {
+  const long i = long(blockIdx.x) * 256 + threadIdx.x;       // one thread per pixel PAIR
+  const int w2 = W / 2;
+  if (i >= long(N) * H * w2) return;
+  const int n = int(i / (long(H) * w2));
+  const int r = int(i - long(n) * H * w2);
+  const int y = r / w2, xp = r - y * w2;
+  const uint8_t* f = frames + long(n) * Hs * Ws * 3;
+  ingest_pair(p, Hs, Ws, H, W, swap, n, y, xp, nhwc8, nchw,
+              [&](int yy, int xx, int c) { return float(f[(long(yy) * Ws + xx) * 3 + c]); });
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -116,5 +204,32 @@ extern "C" int fvp_rasterise_heatmaps(const double* joints, const int32_t* num_p
   hipLaunchKernelGGL(k_rasterise, dim3(ceil_div(H, RB), nimg), dim3(256), size_t(J) * RB * W * sizeof(float),
                      as_stream(s), joints, num_people, P, J, W, H, RB, feat_stride_x, feat_stride_y, sigma, heat_nchw,
                      heat_cl, JP);
+  return launch_status();
+}
+
+extern "C" int fvp_ingest_frames(const uint8_t* frames, int N, int Hs, int Ws, const float inv[6], const float mean[3],
+                                 const float stdv[3], int H, int W, int flags, uint16_t* nhwc8, float* nchw,
+                                 fvp_stream_t s) {
+  FVP_REQUIRE(frames && inv && mean && stdv && (nhwc8 || nchw));
+  FVP_REQUIRE(N >= 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && W % 2 == 0);
+  FVP_REQUIRE((flags & ~(FVP_INGEST_SWAP_RB | FVP_INGEST_GENERAL)) == 0);
+  IngestPrm p;
+  for (int i = 0; i < 6; ++i) {
+    FVP_REQUIRE(std::isfinite(inv[i]));
+    p.inv[i] = inv[i];
+  }
+  for (int c = 0; c < 3; ++c) {
+    FVP_REQUIRE(std::isfinite(mean[c]) && std::isfinite(stdv[c]) && stdv[c] != 0.0f);
+    p.mean[c] = mean[c];
+    p.stdv[c] = stdv[c];
+  }
+  if (N == 0) return 0;
+  FVP_LIMIT(Hs < (1 << 24) && Ws < (1 << 24) && H < (1 << 24) && W < (1 << 24));   // pixel indices exact in fp32
+  const int swap = (flags & FVP_INGEST_SWAP_RB) ? 1 : 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  const long pairs = long(N) * H * (W / 2);
+  FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
+  hipLaunchKernelGGL(k_ingest_gather, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), frames, N, Hs, Ws,
+                     p, H, W, swap, nhwc8, nchw);
   return launch_status();
 }

@@ -10,6 +10,8 @@ import time
 import torch
 import torch.nn as nn
 
+from .. import _capi as capi
+from ..dataset.images import ingest_frames
 from ..engine import HotPath
 from .human_detection_net import HumanDetectionNet
 from .joint_localization_net import JointLocalizationNet
@@ -37,7 +39,24 @@ class FasterVoxelPoseNet(nn.Module):
             raise NotImplementedError("only the inference branch of FasterVoxelPoseNet.forward is implemented "
                                       "(call model.eval()); training losses are outside the hot path")
         if views is not None:
-            if hasattr(backbone, "_run"):
+            frames = views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
+            if frames:
+                if views.dim() != 5 or views.shape[-1] != 3:
+                    raise capi.FvpError(f"uint8 views must be camera frames [B,V,Hs,Ws,3] (HWC), got {tuple(views.shape)}")
+                if resize_transform is None:
+                    raise capi.FvpError("uint8 views need resize_transform (camera -> network pixels) to be resized")
+            if frames and hasattr(backbone, "_run"):
+                # the ingest kernel writes the backbone's bf16 input directly: no fp32 image tensor
+                B, V = views.shape[:2]
+                nchw, cl = backbone._run(views.flatten(0, 1), True, True, resize_transform=resize_transform)
+                input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
+                if cl.shape[-1] == self.engine.JP:
+                    self.engine.adopt_staging(input_heatmaps, cl)
+            elif frames:
+                # any torch module: the fp32 tensor the reference's loader would have produced, then per-view passes
+                views = ingest_frames(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+                input_heatmaps = torch.stack([backbone(views[:, c]) for c in range(views.shape[1])], dim=1)
+            elif hasattr(backbone, "_run"):
                 # bf16 HIP backbone (models/resnet.py): all B*V views in one pass; it writes the heatmaps as
                 # NCHW (returned, like the reference) and in the channels-last layout the projection reads
                 B, V = views.shape[:2]

@@ -6,7 +6,9 @@ The module holds parameters only.  ``forward`` runs the whole network through th
 interpreter ``fvp_bb_run`` (NHWC bf16 activations, implicit-GEMM convs on
 ``v_mfma_f32_32x32x16_bf16`` with fp32 accumulation, eval BatchNorm folded to a scale / shift in the
 epilogue together with the residual add and ReLU).  ``forward_channels_last`` returns the fp32
-heatmaps directly in the ``[N, H*W, JP]`` staging layout the projection kernels read.
+heatmaps directly in the ``[N, H*W, JP]`` staging layout the projection kernels read.  ``forward_frames`` takes raw
+uint8 camera frames instead of the normalised fp32 image: ``fvp_ingest_frames`` (dataset/images.py) writes the bf16
+input buffer directly.
 """
 import ctypes as C
 import os
@@ -14,6 +16,7 @@ import os
 import torch
 
 from .. import _capi as capi
+from ..dataset import images as IMG
 from ..netspec import ParamTree
 
 SPEC = {18: ("basic", [2, 2, 2, 2]), 34: ("basic", [3, 4, 6, 3]), 50: ("bottleneck", [3, 4, 6, 3]),
@@ -36,6 +39,8 @@ class PoseResNet(ParamTree):
         self.__dict__["deconv_bias"] = bool(r.DECONV_WITH_BIAS)
         self.__dict__["num_joints"] = int(cfg.DATASET.NUM_JOINTS)
         self.__dict__["device_name"] = str(cfg.DEVICE)
+        size = getattr(cfg.DATASET, "IMAGE_SIZE", None)
+        self.__dict__["image_size"] = None if size is None else (int(size[0]), int(size[1]))     # (W, H): forward_frames
         dev = torch.device(cfg.DEVICE)
         if _lib is None and dev.type != "cuda":
             raise capi.FvpError("the backbone runs on the GPU only (no CPU fallback)")
@@ -197,9 +202,20 @@ class PoseResNet(ParamTree):
         self.__dict__["_dirty"] = False
 
     # ---- forward ----------------------------------------------------------------------------------------------------
-    def _run(self, x, want_cl, want_nchw):
-        assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
-        N, _, H, W = x.shape
+    def _run(self, x, want_cl, want_nchw, resize_transform=None, swap_rb=True):
+        """``x``: fp32 images [N,3,H,W], or uint8 camera frames [N,Hs,Ws,3] together with ``resize_transform``."""
+        frames = x.dtype == torch.uint8
+        if frames:
+            if x.dim() != 4 or x.shape[-1] != 3:
+                raise capi.FvpError(f"uint8 frames must be [N,Hs,Ws,3] (HWC), got {tuple(x.shape)}")
+            if resize_transform is None:
+                raise capi.FvpError("uint8 frames need resize_transform (camera -> network pixels)")
+            if self.image_size is None:
+                raise capi.FvpError("uint8 frames need cfg.DATASET.IMAGE_SIZE")
+            N, (W, H) = x.shape[0], self.image_size
+        else:
+            assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+            N, _, H, W = x.shape
         assert H % 32 == 0 and W % 32 == 0, "image size must be a multiple of 32"
         dev = x.device
         plan = self._plan(H, W)
@@ -214,8 +230,12 @@ class PoseResNet(ParamTree):
         pool, bufs = {}, [None] * len(plan["names"])
         c, h, w = plan["shapes"]["x"]
         bufs[0] = torch.empty((N, h, w // 2, c), dtype=torch.bfloat16, device=dev)
-        capi.check(self.lib, self.lib.fvp_bb_input(C.c_void_p(x.contiguous().data_ptr()), C.c_void_p(bufs[0].data_ptr()), N, 3,
-                                                   H, W, s), "fvp_bb_input")
+        if frames:                   # warp + swap + normalise + bf16 in one kernel: no fp32 image tensor exists
+            IMG.launch(self.lib, x.contiguous(), resize_transform, (W, H), swap_rb, IMG.IMAGENET_MEAN, IMG.IMAGENET_STD,
+                       bufs[0], None)
+        else:
+            capi.check(self.lib, self.lib.fvp_bb_input(C.c_void_p(x.contiguous().data_ptr()), C.c_void_p(bufs[0].data_ptr()), N, 3,
+                                                       H, W, s), "fvp_bb_input")
         for i, op in enumerate(plan["ops"]):                     # allocation plan only (launch order = op order)
             if op.dst >= 0:
                 c, h, w = plan["shapes"][plan["names"][op.dst]]
@@ -250,6 +270,12 @@ class PoseResNet(ParamTree):
     def forward(self, x):
         """[N,3,H,W] fp32 images -> [N,J,H/4,W/4] fp32 heatmaps (resnet.py:184-199)."""
         return self._run(x, False, True)[0]
+
+    def forward_frames(self, frames, resize_transform, swap_rb=True):
+        """uint8 camera frames [N,Hs,Ws,3] (HWC, native resolution; BGR with ``swap_rb``) -> [N,J,H/4,W/4] fp32 heatmaps
+        at cfg.DATASET.IMAGE_SIZE: the reference's offline warpAffine + loader transform + backbone.  ``resize_transform``
+        is the forward 2x3 of ``get_resize_transform``."""
+        return self._run(frames, False, True, resize_transform=resize_transform, swap_rb=swap_rb)[0]
 
     def forward_channels_last(self, x):
         """Heatmaps as [N, H/4 * W/4, JP] fp32 (JP = J rounded up to 4, padding channels zero)."""

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 8
+#define FVP_ABI_VERSION 9
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -273,6 +273,32 @@ int fvp_fuse_poses(const float* pose2d, const float* pmax, const float* wgt, con
 int fvp_rasterise_heatmaps(const double* joints, const int32_t* num_people, int nimg, int P, int J, int W, int H,
                            double feat_stride_x, double feat_stride_y, double sigma, float* heat_nchw,
                            float* heat_cl, int JP, fvp_stream_t s);
+
+/* ---- "next" row f-3: camera frames -> backbone input ---------------------------------------------------
+ * frames [N][Hs][Ws][3] uint8 HWC at the camera's resolution (contiguous) -> the network image of H x W:
+ * bilinear warp + channel swap + / 255 + mean / std in one pass.  Replaces the reference's offline resize
+ * (preprocess.py: cv2.warpAffine(image, trans, image_size, flags=INTER_LINEAR) with the matrix of
+ * get_resize_transform) and its loader (lib/dataset/JointsDataset.py:129-133 imread / BGR->RGB / transform,
+ * run/validate.py:44-52 ToTensor + Normalize).
+ *   inv  [6]  HOST memory, passed to the kernel by value: destination pixel -> source pixel, row-major 2x3 (the
+ *             inverse of resize_transform);
+ *   mean, stdv [3]  HOST memory, by value, in OUTPUT channel order;
+ *   flags     FVP_INGEST_SWAP_RB: output channel c reads source channel 2 - c (COLOR_BGR2RGB);
+ *             FVP_INGEST_GENERAL: accepted, no effect - the general (gather) form is the only one shipped; an
+ *             LDS-staged form for axis-aligned matrices computed the same bits and was not faster;
+ *   nhwc8     (may be NULL) [N][H][W/2] pixel pairs of 8 bf16 = fvp_bb_input's layout, channel 3 = 0;
+ *   nchw      (may be NULL) [N][3][H][W] fp32 (torch backbones, tests).  W even.
+ * Arithmetic, fp32, every operation rounded on its own (no fma, IEEE divisions), x, y = destination pixel:
+ *   sx = inv[0]*x + inv[1]*y + inv[2],  sy = inv[3]*x + inv[4]*y + inv[5]          (left to right)
+ *   x0 = floor(sx), y0 = floor(sy), fx = sx - x0, fy = sy - y0
+ *   p00..p11 = the four source bytes of the channel; a tap outside [0,Ws) x [0,Hs) is 0 (BORDER_CONSTANT 0)
+ *   v   = (1-fy)*((1-fx)*p00 + fx*p01) + fy*((1-fx)*p10 + fx*p11)
+ *   out = ((v / 255) - mean[c]) / stdv[c];   bf16 = round-to-nearest-even of out (as fvp_bb_input)
+ * With the identity matrix and Hs, Ws == H, W this is ToTensor + Normalize in fp32.  Not bit-compatible with
+ * OpenCV's fixed-point INTER_LINEAR.  N == 0 returns 0 without a launch. */
+enum { FVP_INGEST_SWAP_RB = 1, FVP_INGEST_GENERAL = 2 };
+int fvp_ingest_frames(const uint8_t* frames, int N, int Hs, int Ws, const float inv[6], const float mean[3],
+                      const float stdv[3], int H, int W, int flags, uint16_t* nhwc8, float* nchw, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

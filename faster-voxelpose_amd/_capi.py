@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 9            # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 10           # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -23,6 +23,7 @@ BB_CONV, BB_MAXPOOL, BB_DECONV = 0, 1, 2
 BB_OUT_HEAT = 8
 BB_STEM = 16
 INGEST_SWAP_RB, INGEST_GENERAL = 1, 2
+YUV_BT601_LIMITED, YUV_BT709_LIMITED, YUV_BT601_FULL, YUV_BT709_FULL = 0, 1, 2, 3
 
 
 class FvpGeom(C.Structure):
@@ -75,6 +76,8 @@ SIGNATURES = {
     "fvp_fuse_poses": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "fvp_rasterise_heatmaps": [_P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _I, _P],
     "fvp_ingest_frames": [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I, _I, _P, _P, _P],
+    "fvp_ingest_nv12": [_P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, C.POINTER(_F), C.POINTER(_F),
+                        C.POINTER(_F), _I, _I, _P, _P, _P],
     "fvp_bb_input": [_P, _P, _I, _I, _I, _I, _P],
     "fvp_bb_pack": [_P, _P, _P, _P, _P, _P, _F, C.POINTER(FvpBbOp), _P, _P, _P],
     "fvp_bb_run": [C.POINTER(FvpBbOp), _I, _P, _P, C.POINTER(_P), _I, _I, _P, _I, _P, _P],

@@ -112,7 +112,7 @@ k_rasterise(const double* __restrict__ joints, const int* __restrict__ num_peopl
 // (k_bb_input's layout) and / or as the fp32 NCHW tensor a torch backbone reads.  Memory traffic only: one lane per
 // destination pixel PAIR, one 16-byte store.
 //
-// The arithmetic is fixed (include/fvp.h) and lives in ingest_pair(), which takes the source of a tap's byte as a
+// The arithmetic is fixed (include/fvp.h) and lives in ingest_pair(), which takes the source of a tap's pixel as a
 // functor.  One form ships: k_ingest_gather reads the bytes from global memory (any matrix).  A second form that first
 // copied the source rectangle of a 128 x 4 destination tile into LDS with 16-byte loads (rows realigned by their byte
 // offset) computed the same bits but was not faster on the card - 257 us against 192 us for 40 frames 1080p -> 512x960,
@@ -136,13 +136,17 @@ __device__ __forceinline__ float ingest_coord(float a, float b, float c, int x, 
 // floor() of a source coordinate as an int; anything that cannot have a tap inside [0, n) becomes -2 (both taps outside)
 __device__ __forceinline__ int ingest_cell(float fl, int n) { return (fl >= -1.0f && fl < float(n)) ? int(fl) : -2; }
 
-// Destination pixels (2 * xp, y) and (2 * xp + 1, y) of image n.  tap(yy, xx, c) = source byte as float, both
-// coordinates already inside the frame.
+struct IngestPx { float c[3]; };                            // one source pixel, OUTPUT channel order
+
+// Destination pixels (2 * xp, y) and (2 * xp + 1, y) of image n.  tap(yy, xx) = the source pixel as three floats in
+// output channel order, both coordinates already inside the frame; it is called once per in-frame tap and feeds the
+// three bilinear evaluations (an NV12 tap converts to R, G, B there, once).
 template <class Tap>
-__device__ __forceinline__ void ingest_pair(const IngestPrm& p, int Hs, int Ws, int H, int W, int swap, int n, int y, int xp,
+__device__ __forceinline__ void ingest_pair(const IngestPrm& p, int Hs, int Ws, int H, int W, int n, int y, int xp,
                                             uint16_t* __restrict__ nhwc8, float* __restrict__ nchw, Tap tap) {
   uint16_t v16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const long hw = long(H) * W;
+  const IngestPx zero = {{0.0f, 0.0f, 0.0f}};
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int x = 2 * xp + e;
@@ -153,12 +157,11 @@ __device__ __forceinline__ void ingest_pair(const IngestPrm& p, int Hs, int Ws, 
     const int x0 = ingest_cell(flx, Ws), y0 = ingest_cell(fly, Hs);
     const bool xa = x0 >= 0, xb = x0 + 1 >= 0 && x0 + 1 < Ws, ya = y0 >= 0, yb = y0 + 1 >= 0 && y0 + 1 < Hs;
     const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const IngestPx p00 = ya && xa ? tap(y0, x0) : zero, p01 = ya && xb ? tap(y0, x0 + 1) : zero;
+    const IngestPx p10 = yb && xa ? tap(y0 + 1, x0) : zero, p11 = yb && xb ? tap(y0 + 1, x0 + 1) : zero;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const int sc = swap ? 2 - c : c;
-      const float p00 = ya && xa ? tap(y0, x0, sc) : 0.0f, p01 = ya && xb ? tap(y0, x0 + 1, sc) : 0.0f;
-      const float p10 = yb && xa ? tap(y0 + 1, x0, sc) : 0.0f, p11 = yb && xb ? tap(y0 + 1, x0 + 1, sc) : 0.0f;
-      const float v = gy * (gx * p00 + fx * p01) + fy * (gx * p10 + fx * p11);
+      const float v = gy * (gx * p00.c[c] + fx * p01.c[c]) + fy * (gx * p10.c[c] + fx * p11.c[c]);
       const float o = __fdiv_rn(__fdiv_rn(v, 255.0f) - p.mean[c], p.stdv[c]);
       v16[4 * e + c] = ingest_f2bf(o);
       if (nchw) nchw[(long(n) * 3 + c) * hw + long(y) * W + x] = o;
@@ -183,8 +186,44 @@ k_ingest_gather(const uint8_t* __restrict__ frames, int N, int Hs, int Ws, Inges
   const int r = int(i - long(n) * H * w2);
   const int y = r / w2, xp = r - y * w2;
   const uint8_t* f = frames + long(n) * Hs * Ws * 3;
-  ingest_pair(p, Hs, Ws, H, W, swap, n, y, xp, nhwc8, nchw,
-              [&](int yy, int xx, int c) { return float(f[(long(yy) * Ws + xx) * 3 + c]); });
+  const int c0 = swap ? 2 : 0, c2 = 2 - c0;
+  ingest_pair(p, Hs, Ws, H, W, n, y, xp, nhwc8, nchw, [&](int yy, int xx) {
+    const uint8_t* q = f + (long(yy) * Ws + xx) * 3;
+    return IngestPx{{float(q[c0]), float(q[1]), float(q[c2])}};
+  });
+}
+
+// NV12 surface (include/fvp.h): a tap is one luma byte and the (U, V) pair of its 2 x 2 quad as ONE 2-byte load,
+// converted to R, G, B in int32 once.  8 + 8 loads per lane against the 24 of k_ingest_gather, 1.5 source bytes per pixel
+// against 3.  Neighbouring taps that share a chroma sample load it again (same cache line).
+struct Nv12Prm {
+  long y_pitch, uv_pitch, y_frame, uv_frame;
+  int yoff, cy, crv, cgu, cgv, cbu;
+};
+
+__device__ __forceinline__ float ingest_clip8(int v) {      // (v >> 20) clipped to a byte; >> is arithmetic
+  const int b = v >> 20;
+  return float(b < 0 ? 0 : b > 255 ? 255 : b);
+}
+
+__global__ void __launch_bounds__(256)
+k_ingest_nv12(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, int N, int Hs, int Ws, Nv12Prm q,
+              IngestPrm p, int H, int W, uint16_t* __restrict__ nhwc8, float* __restrict__ nchw) {
+  const long i = long(blockIdx.x) * 256 + threadIdx.x;       // one thread per pixel PAIR
+  const int w2 = W / 2;
+  if (i >= long(N) * H * w2) return;
+  const int n = int(i / (long(H) * w2));
+  const int r = int(i - long(n) * H * w2);
+  const int y = r / w2, xp = r - y * w2;
+  const uint8_t* fy = yp + long(n) * q.y_frame;
+  const uint8_t* fuv = uvp + long(n) * q.uv_frame;
+  ingest_pair(p, Hs, Ws, H, W, n, y, xp, nhwc8, nchw, [&](int yy, int xx) {
+    const int luma = fy[long(yy) * q.y_pitch + xx];
+    const uint32_t w = *reinterpret_cast<const uint16_t*>(fuv + long(yy >> 1) * q.uv_pitch + 2 * (xx >> 1));
+    const int c = luma > q.yoff ? luma - q.yoff : 0, d = int(w & 0xffu) - 128, e = int(w >> 8) - 128;
+    const int l = q.cy * c + (1 << 19);
+    return IngestPx{{ingest_clip8(l + q.crv * e), ingest_clip8(l + q.cgu * d + q.cgv * e), ingest_clip8(l + q.cbu * d)}};
+  });
 }
 
 }  // namespace fvp
@@ -231,5 +270,39 @@ extern "C" int fvp_ingest_frames(const uint8_t* frames, int N, int Hs, int Ws, c
   FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
   hipLaunchKernelGGL(k_ingest_gather, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), frames, N, Hs, Ws,
                      p, H, W, swap, nhwc8, nchw);
+  return launch_status();
+}
+
+extern "C" int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int Hs, int Ws, long y_pitch, long uv_pitch,
+                               long y_frame_stride, long uv_frame_stride, int standard, const float inv[6],
+                               const float mean[3], const float stdv[3], int H, int W, uint16_t* nhwc8, float* nchw,
+                               fvp_stream_t s) {
+  static const int coeffs[4][6] = {FVP_YUV_BT601_LIMITED_COEFFS, FVP_YUV_BT709_LIMITED_COEFFS, FVP_YUV_BT601_FULL_COEFFS,
+                                   FVP_YUV_BT709_FULL_COEFFS};
+  FVP_REQUIRE(y && uv && inv && mean && stdv && (nhwc8 || nchw));
+  FVP_REQUIRE(N >= 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && Hs % 2 == 0 && Ws % 2 == 0 && W % 2 == 0);
+  FVP_REQUIRE(y_pitch >= Ws && uv_pitch >= Ws);
+  // a (U, V) pair is one 2-byte load
+  FVP_REQUIRE(uv_pitch % 2 == 0 && uv_frame_stride % 2 == 0 && reinterpret_cast<uintptr_t>(uv) % 2 == 0);
+  FVP_REQUIRE(standard >= 0 && standard < 4);
+  IngestPrm p;
+  for (int i = 0; i < 6; ++i) {
+    FVP_REQUIRE(std::isfinite(inv[i]));
+    p.inv[i] = inv[i];
+  }
+  for (int c = 0; c < 3; ++c) {
+    FVP_REQUIRE(std::isfinite(mean[c]) && std::isfinite(stdv[c]) && stdv[c] != 0.0f);
+    p.mean[c] = mean[c];
+    p.stdv[c] = stdv[c];
+  }
+  if (N == 0) return 0;
+  FVP_LIMIT(Hs < (1 << 24) && Ws < (1 << 24) && H < (1 << 24) && W < (1 << 24));   // pixel indices exact in fp32
+  const int* k = coeffs[standard];
+  const Nv12Prm q = {y_pitch, uv_pitch, y_frame_stride, uv_frame_stride, k[0], k[1], k[2], k[3], k[4], k[5]};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  const long pairs = long(N) * H * (W / 2);
+  FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
+  hipLaunchKernelGGL(k_ingest_nv12, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), y, uv, N, Hs, Ws, q,
+                     p, H, W, nhwc8, nchw);
   return launch_status();
 }

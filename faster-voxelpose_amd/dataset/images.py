@@ -8,6 +8,11 @@ Device side: ``fvp_ingest_frames`` (csrc/fvp_heatmap.hip) - bilinear warp with z
 mean / std, written as fp32 ``[N,3,H,W]`` and / or straight into the bf16 input buffer of the HIP backbone
 (``PoseResNet.forward_frames``).  The arithmetic is spelled out in ``include/fvp.h``; it is NOT bit-compatible with
 OpenCV's fixed-point INTER_LINEAR.
+
+NV12 surfaces - what a hardware decoder or a capture card leaves in device memory - go in without an RGB frame in
+between: ``Nv12Frames`` describes the two planes (pitch and frame stride are the tensors' strides), ``ingest_nv12`` /
+``launch_nv12`` call ``fvp_ingest_nv12``, whose outputs equal ``fvp_ingest_frames`` on the frame converted pixel by
+pixel with the integer formula of ``include/fvp.h``.
 """
 import ctypes as C
 
@@ -99,3 +104,119 @@ def ingest_frames(frames, resize_transform, image_size, swap_rb=True, mean=IMAGE
         raise capi.FvpError(f"out must be a contiguous float32 tensor of {shape} on {frames.device}")
     launch(lib, flat, resize_transform, (W, H), swap_rb, mean, std, None, out)
     return out.view(*lead, 3, H, W)
+
+
+YUV_STANDARDS = {("bt601", False): capi.YUV_BT601_LIMITED, ("bt709", False): capi.YUV_BT709_LIMITED,
+                 ("bt601", True): capi.YUV_BT601_FULL, ("bt709", True): capi.YUV_BT709_FULL}
+
+
+def _frame_stride(t, nlead, what):
+    """Element stride from frame to frame of ``t`` whose first ``nlead`` dimensions count frames: they must flatten to
+    one constant stride (None when there is a single frame: any stride does)."""
+    dims = [(n, st) for n, st in zip(t.shape[:nlead], t.stride()[:nlead]) if n != 1]
+    for (_, outer), (n, inner) in zip(dims, dims[1:]):
+        if outer != n * inner:
+            raise capi.FvpError(f"{what}: the leading dimensions {tuple(t.shape[:nlead])} with strides "
+                                f"{tuple(t.stride()[:nlead])} do not flatten to one constant frame stride")
+    return dims[-1][1] if dims else None
+
+
+class Nv12Frames:
+    """NV12 camera frames in device memory, as two views of the decoder's surface (no copy):
+
+    ``y``   uint8 ``[..., Hs, Ws]``: the luma plane; ``uv`` uint8 ``[..., Hs/2, Ws/2, 2]``: the interleaved (U, V) plane,
+    same leading dimensions.  The last dimension of ``y`` and the last two of ``uv`` are dense; the row stride is the
+    surface's pitch and the stride between frames is free, as long as the leading dimensions flatten to one constant
+    frame stride.  ``standard``: ``"bt601"`` or ``"bt709"``; ``full_range``: 0..255 luma instead of 16..235."""
+
+    def __init__(self, y, uv, standard="bt601", full_range=False):
+        key = (str(standard).lower(), bool(full_range))
+        if key not in YUV_STANDARDS:
+            raise capi.FvpError(f"unknown colour standard {standard!r} (bt601 or bt709)")
+        for name, t in (("y", y), ("uv", uv)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                raise capi.FvpError(f"{name} must be a uint8 tensor")
+        if y.dim() < 2 or uv.dim() != y.dim() + 1 or uv.shape[-1] != 2:
+            raise capi.FvpError(f"y must be [...,Hs,Ws] and uv [...,Hs/2,Ws/2,2], got {tuple(y.shape)} and {tuple(uv.shape)}")
+        Hs, Ws = int(y.shape[-2]), int(y.shape[-1])
+        if Hs < 2 or Ws < 2 or Hs % 2 or Ws % 2:
+            raise capi.FvpError(f"NV12 frames have even, non-zero height and width, got {Hs} x {Ws}")
+        if tuple(uv.shape[-3:-1]) != (Hs // 2, Ws // 2):
+            raise capi.FvpError(f"uv must be [...,{Hs // 2},{Ws // 2},2] for y [...,{Hs},{Ws}], got {tuple(uv.shape)}")
+        if tuple(y.shape[:-2]) != tuple(uv.shape[:-3]):
+            raise capi.FvpError(f"y and uv differ in their leading dimensions: {tuple(y.shape[:-2])} and {tuple(uv.shape[:-3])}")
+        if y.device != uv.device:
+            raise capi.FvpError("y and uv are on different devices")
+        if y.stride(-1) != 1 or uv.stride(-1) != 1 or uv.stride(-2) != 2:
+            raise capi.FvpError("the last dimension of y and the last two of uv must be dense (a row is Ws bytes in a "
+                                "row, only the pitch between rows is free)")
+        self.y, self.uv, self.standard = y, uv, YUV_STANDARDS[key]
+        self.lead = tuple(y.shape[:-2])
+        self.N = 1
+        for n in self.lead:
+            self.N *= int(n)
+        self.Hs, self.Ws = Hs, Ws
+        self.y_pitch, self.uv_pitch = int(y.stride(-2)), int(uv.stride(-3))
+        nlead = len(self.lead)
+        ys, us = _frame_stride(y, nlead, "y"), _frame_stride(uv, nlead, "uv")
+        self.y_frame_stride = int(ys) if ys is not None else Hs * self.y_pitch
+        self.uv_frame_stride = int(us) if us is not None else (Hs // 2) * self.uv_pitch
+        self.device, self.is_cuda = y.device, y.is_cuda
+
+    @classmethod
+    def from_buffer(cls, buf, height, width, pitch=None, standard="bt601", full_range=False):
+        """The layout a decoder hands out: ``buf`` uint8 ``[..., Hs*3/2, pitch]`` - Hs rows of luma, then Hs/2 rows of
+        interleaved chroma, ``pitch >= Ws`` bytes per row (``pitch`` defaults to the last dimension; with ``pitch``
+        given, a flat ``[..., Hs*3/2 * pitch]`` buffer is accepted too).  The two planes are views of ``buf``."""
+        Hs, Ws = int(height), int(width)
+        if Hs < 2 or Ws < 2 or Hs % 2 or Ws % 2:
+            raise capi.FvpError(f"NV12 frames have even, non-zero height and width, got {Hs} x {Ws}")
+        rows = Hs * 3 // 2
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() < 1:
+            raise capi.FvpError("buf must be a uint8 tensor")
+        if pitch is not None and (buf.dim() < 2 or buf.shape[-1] != int(pitch) or buf.shape[-2] != rows):
+            if buf.shape[-1] != rows * int(pitch) or buf.stride(-1) != 1:
+                raise capi.FvpError(f"buf {tuple(buf.shape)} is neither [...,{rows},{pitch}] nor [...,{rows * int(pitch)}]")
+            buf = buf.unflatten(-1, (rows, int(pitch)))
+        if buf.dim() < 2 or buf.shape[-2] != rows or buf.shape[-1] < Ws:
+            raise capi.FvpError(f"buf must be [...,{rows},pitch >= {Ws}] for {Hs} x {Ws} frames, got {tuple(buf.shape)}")
+        if buf.stride(-1) != 1:
+            raise capi.FvpError("the rows of buf must be dense")
+        y = buf[..., :Hs, :Ws]
+        uv = buf[..., Hs:, :Ws].unflatten(-1, (Ws // 2, 2))
+        return cls(y, uv, standard, full_range)
+
+
+def launch_nv12(lib, frames, resize_transform, image_size, mean, std, nhwc8, nchw):
+    """One ``fvp_ingest_nv12`` call on the current stream: the NV12 counterpart of ``launch`` (same cached inverse)."""
+    if not isinstance(frames, Nv12Frames):
+        raise capi.FvpError(f"frames must be Nv12Frames, got {type(frames).__name__}")
+    W, H = int(image_size[0]), int(image_size[1])
+    inv = _inverse.get(resize_transform)
+    stream = C.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream) if frames.is_cuda else None
+    rc = lib.fvp_ingest_nv12(C.c_void_p(frames.y.data_ptr()), C.c_void_p(frames.uv.data_ptr()), frames.N, frames.Hs,
+                             frames.Ws, frames.y_pitch, frames.uv_pitch, frames.y_frame_stride, frames.uv_frame_stride,
+                             frames.standard, (C.c_float * 6)(*[float(v) for v in inv]), _f3(mean), _f3(std), H, W,
+                             C.c_void_p(nhwc8.data_ptr()) if nhwc8 is not None else None,
+                             C.c_void_p(nchw.data_ptr()) if nchw is not None else None, stream)
+    capi.check(lib, rc, "fvp_ingest_nv12")
+
+
+def ingest_nv12(frames, resize_transform, image_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, _lib=None):
+    """``frames``: ``Nv12Frames`` on the GPU with leading dimensions ``[...]``; ``resize_transform`` and ``image_size``
+    as for ``ingest_frames``.  Returns fp32 ``[...,3,H,W]``, RGB order: bit for bit what ``ingest_frames(...,
+    swap_rb=False)`` returns for the frames converted to RGB with the integer formula of ``include/fvp.h``."""
+    if not isinstance(frames, Nv12Frames):
+        raise capi.FvpError(f"frames must be Nv12Frames, got {type(frames).__name__}")
+    if _lib is None and not frames.is_cuda:
+        raise capi.FvpError("ingest_nv12 runs on the GPU only (no CPU fallback)")
+    lib = _lib if _lib is not None else capi.load()
+    W, H = int(image_size[0]), int(image_size[1])
+    shape = (frames.N, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif out.dtype != torch.float32 or out.numel() != frames.N * 3 * H * W or not out.is_contiguous() \
+            or out.device != frames.device:
+        raise capi.FvpError(f"out must be a contiguous float32 tensor of {shape} on {frames.device}")
+    launch_nv12(lib, frames, resize_transform, (W, H), mean, std, None, out)
+    return out.view(*frames.lead, 3, H, W)

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .. import _capi as capi
-from ..dataset.images import ingest_frames
+from ..dataset.images import Nv12Frames, ingest_frames, ingest_nv12
 from ..engine import HotPath
 from .human_detection_net import HumanDetectionNet
 from .joint_localization_net import JointLocalizationNet
@@ -39,13 +39,31 @@ class FasterVoxelPoseNet(nn.Module):
             raise NotImplementedError("only the inference branch of FasterVoxelPoseNet.forward is implemented "
                                       "(call model.eval()); training losses are outside the hot path")
         if views is not None:
-            frames = views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
-            if frames:
+            nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]
+            frames = not nv12 and views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
+            if nv12:
+                if len(views.lead) != 2:
+                    raise capi.FvpError(f"NV12 views must have leading dimensions [B,V], got {views.lead}")
+                if resize_transform is None:
+                    raise capi.FvpError("NV12 views need resize_transform (camera -> network pixels) to be resized")
+                B, V = views.lead
+                if hasattr(backbone, "_run"):
+                    # the ingest kernel reads the surface and writes the backbone's bf16 input: no RGB frame, no fp32 image
+                    nchw, cl = backbone._run(views, True, True, resize_transform=resize_transform)
+                    input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
+                    if cl.shape[-1] == self.engine.JP:
+                        self.engine.adopt_staging(input_heatmaps, cl)
+                else:
+                    views = ingest_nv12(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+                    input_heatmaps = torch.stack([backbone(views[:, c]) for c in range(V)], dim=1)
+            elif frames:
                 if views.dim() != 5 or views.shape[-1] != 3:
                     raise capi.FvpError(f"uint8 views must be camera frames [B,V,Hs,Ws,3] (HWC), got {tuple(views.shape)}")
                 if resize_transform is None:
                     raise capi.FvpError("uint8 views need resize_transform (camera -> network pixels) to be resized")
-            if frames and hasattr(backbone, "_run"):
+            if nv12:
+                pass                                      # done above; tensor views below take the path they took
+            elif frames and hasattr(backbone, "_run"):
                 # the ingest kernel writes the backbone's bf16 input directly: no fp32 image tensor
                 B, V = views.shape[:2]
                 nchw, cl = backbone._run(views.flatten(0, 1), True, True, resize_transform=resize_transform)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 9
+#define FVP_ABI_VERSION 10
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -299,6 +299,45 @@ int fvp_rasterise_heatmaps(const double* joints, const int32_t* num_people, int 
 enum { FVP_INGEST_SWAP_RB = 1, FVP_INGEST_GENERAL = 2 };
 int fvp_ingest_frames(const uint8_t* frames, int N, int Hs, int Ws, const float inv[6], const float mean[3],
                       const float stdv[3], int H, int W, int flags, uint16_t* nhwc8, float* nchw, fvp_stream_t s);
+
+/* ---- NV12 camera frames -> backbone input (ABI 10) ------------------------------------------------------
+ * The surface a hardware decoder or a capture card leaves in device memory, read directly: colour conversion +
+ * bilinear warp + / 255 + mean / std in one pass, no RGB frame in between.  An NV12 frame of Hs x Ws (both even):
+ *   y   Hs rows of Ws luma bytes, y_pitch bytes from row to row, y_frame_stride bytes from frame to frame;
+ *   uv  Hs/2 rows of Ws/2 interleaved (U, V) byte pairs, uv_pitch bytes from row to row, uv_frame_stride bytes
+ *       from frame to frame.  y and uv are separate DEVICE pointers: uv = y + Hs * pitch for a contiguous NV12
+ *       buffer, or a plane of its own.  A (U, V) pair is read as one 2-byte load: uv, uv_pitch and
+ *       uv_frame_stride must be even.
+ * The SOURCE RGB PIXEL at integer (xi, yi) is defined in int32 arithmetic; chroma is replicated, not
+ * interpolated (the sample at (xi >> 1, yi >> 1) serves its 2 x 2 luma quad):
+ *   c = max(0, Y[yi][xi] - yoff)      d = U[yi>>1][xi>>1] - 128      e = V[yi>>1][xi>>1] - 128
+ *   R = clip(0, 255, (CY*c + CRV*e          + (1 << 19)) >> 20)          (>> is arithmetic: floor)
+ *   G = clip(0, 255, (CY*c + CGU*d + CGV*e  + (1 << 19)) >> 20)
+ *   B = clip(0, 255, (CY*c + CBU*d          + (1 << 19)) >> 20)
+ * with the constants of the colour standard below: round(k * 2^20) of the standard's float64 coefficients
+ * (limited range: yoff 16, luma gain 255/219, chroma gain g = 255/224; full range: yoff 0, gains 1;
+ * CRV = 2(1-Kr)g, CBU = 2(1-Kb)g, CGU = -CBU*Kb/Kg, CGV = -CRV*Kr/Kg; BT.601 Kr 0.299 Kb 0.114, BT.709 Kr 0.2126
+ * Kb 0.0722).  Every intermediate stays below 5.8e8 in magnitude.  No bit-compatibility with any particular
+ * library's converter is claimed.
+ * From the source RGB pixel on, the arithmetic is exactly that of fvp_ingest_frames with flags = 0 (output channel 0
+ * is R): coordinates through inv, floor, four taps with a zero border (a tap outside [0,Ws) x [0,Hs) is 0 and is
+ * not converted), the same fp32 bilinear expression, / 255, - mean, / stdv, bf16 round-to-nearest-even.  Hence:
+ * THE OUTPUTS OF fvp_ingest_nv12 EQUAL, BIT FOR BIT, fvp_ingest_frames APPLIED TO THE RGB uint8 FRAME OBTAINED BY
+ * CONVERTING EVERY SOURCE PIXEL WITH THE FORMULA ABOVE.
+ * inv, mean, stdv: HOST memory, by value, as for fvp_ingest_frames; nhwc8 / nchw as there (either may be NULL).
+ * FVP_EINVAL: a null pointer or both outputs null; odd Hs, Ws or W; y_pitch < Ws or uv_pitch < Ws; odd uv_pitch,
+ * uv address or uv_frame_stride; unknown standard; non-finite inv / mean / stdv or stdv == 0.  FVP_ELIMIT as
+ * fvp_ingest_frames.  N == 0 returns 0 without a launch. */
+enum { FVP_YUV_BT601_LIMITED = 0, FVP_YUV_BT709_LIMITED = 1, FVP_YUV_BT601_FULL = 2, FVP_YUV_BT709_FULL = 3 };
+/*                                      yoff  CY       CRV      CGU      CGV      CBU */
+#define FVP_YUV_BT601_LIMITED_COEFFS { 16, 1220945, 1673555, -410793, -852458, 2115221 }
+#define FVP_YUV_BT709_LIMITED_COEFFS { 16, 1220945, 1879825, -223607, -558796, 2215014 }
+#define FVP_YUV_BT601_FULL_COEFFS { 0, 1048576, 1470104, -360853, -748826, 1858077 }
+#define FVP_YUV_BT709_FULL_COEFFS { 0, 1048576, 1651297, -196424, -490864, 1945738 }
+int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int Hs, int Ws, long y_pitch, long uv_pitch,
+                    long y_frame_stride, long uv_frame_stride, /* bytes */
+                    int standard, const float inv[6], const float mean[3], const float stdv[3], int H, int W,
+                    uint16_t* nhwc8, float* nchw, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

@@ -24,8 +24,10 @@ static_assert(sizeof(Cam) == FVP_CAM_FLOATS * sizeof(float), "camera record size
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
-__device__ __forceinline__ void project_norm(const Cam& cm, const FvpGeom& g, float wx, float wy, float wz,
-                                             float& gx, float& gy) {
+// Distorted pixel of a world point in the ORIGINAL camera image (cameras.py:30-56), before any clamp, and its
+// camera-space depth (xcam[2], before the +1e-5 of :44).  The one copy of the camera model.
+__device__ __forceinline__ void project_pixel(const Cam& cm, float wx, float wy, float wz, float& px, float& py,
+                                              float& depth) {
   const float d0 = __fsub_rn(wx, cm.T[0]), d1 = __fsub_rn(wy, cm.T[1]), d2 = __fsub_rn(wz, cm.T[2]);
   const float xc0 = __fmaf_rn(cm.R[2], d2, __fmaf_rn(cm.R[1], d1, __fmul_rn(cm.R[0], d0)));
   const float xc1 = __fmaf_rn(cm.R[5], d2, __fmaf_rn(cm.R[4], d1, __fmul_rn(cm.R[3], d0)));
@@ -42,8 +44,13 @@ __device__ __forceinline__ void project_norm(const Cam& cm, const FvpGeom& g, fl
   u = __fadd_rn(u, __fmul_rn(cm.p[1], __fadd_rn(r, __fmul_rn(__fmul_rn(2.0f, y0), y0))));
   float v = __fadd_rn(__fmul_rn(y1, d), __fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[1]), y0), y1));
   v = __fadd_rn(v, __fmul_rn(cm.p[0], __fadd_rn(r, __fmul_rn(__fmul_rn(2.0f, y1), y1))));
-  float px = __fadd_rn(__fmul_rn(cm.f[0], u), cm.c[0]);
-  float py = __fadd_rn(__fmul_rn(cm.f[1], v), cm.c[1]);
+  px = __fadd_rn(__fmul_rn(cm.f[0], u), cm.c[0]);
+  py = __fadd_rn(__fmul_rn(cm.f[1], v), cm.c[1]);
+  depth = xc2;
+}
+
+// Original-image pixel -> normalised grid_sample coordinate (project_whole.py:51-59).
+__device__ __forceinline__ void pixel_to_norm(const FvpGeom& g, float px, float py, float& gx, float& gy) {
   // torch.clamp(x, lo, hi) = min(max(x, lo), hi); NaN is undefined behaviour in the reference
   px = clampf(px, -1.0f, g.clamp_max);
   py = clampf(py, -1.0f, g.clamp_max);
@@ -55,6 +62,13 @@ __device__ __forceinline__ void project_norm(const Cam& cm, const FvpGeom& g, fl
   sy = __fsub_rn(__fmul_rn(__fdiv_rn(sy, __fsub_rn(g.hm_h, 1.0f)), 2.0f), 1.0f);
   gx = clampf(sx, -1.1f, 1.1f);
   gy = clampf(sy, -1.1f, 1.1f);
+}
+
+__device__ __forceinline__ void project_norm(const Cam& cm, const FvpGeom& g, float wx, float wy, float wz,
+                                             float& gx, float& gy) {
+  float px, py, depth;
+  project_pixel(cm, wx, wy, wz, px, py, depth);
+  pixel_to_norm(g, px, py, gx, gy);
 }
 
 // Bilinear taps of F.grid_sample(align_corners=True, padding 'zeros'): tap order nw, ne, sw,

@@ -84,6 +84,54 @@ __device__ __forceinline__ void backproject_point(const float* __restrict__ heat
 }
 
 // ---------------------------------------------------------------------------------------------
+// Joint evidence: what backproject_point would put into a voxel centred on each fused joint, kept per view.
+// One lane per (frame, person slot, joint) walks the views in order; channel j is one scalar load per tap
+// (the value sample_view computes for that channel: same taps, weights and fma chain).  A few thousand items:
+// the launch is latency-bound, nothing here is tuned.
+//   views[b][v][n][j] = (px, py, depth, s_v)   pixel in the original image before the clamp, camera-space z
+//   conf[b][n][j]     = clamp01((s_0 + ... + s_{V-1}) / V)
+// Slots with fused[b][n][0][3] < 0 are written as zeros.
+__global__ void __launch_bounds__(256)
+k_joint_evidence(const float* __restrict__ heat_cl, const Cam* __restrict__ cams, const int* __restrict__ frame_set,
+                 const float* __restrict__ fused, int B, int N, FvpGeom g, float* __restrict__ views,
+                 float* __restrict__ conf) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int J = g.J, JP = g.JP;
+  if (i >= B * N * J) return;
+  const int bn = i / J, j = i - bn * J;
+  const int b = bn / N, n = bn - b * N;
+  const bool valid = fused[size_t(bn) * J * 5 + 3] >= 0.0f;
+  const float* p = fused + size_t(i) * 5;
+  const float wx = p[0], wy = p[1], wz = p[2];
+  const size_t view_stride = size_t(g.H) * g.W * JP;
+  const float* frame = heat_cl + size_t(b) * g.V * view_stride;
+  const Cam* cm = cams + size_t(frame_set[b]) * g.V;
+  float acc = 0.0f;
+  for (int v = 0; v < g.V; ++v) {
+    float px = 0.0f, py = 0.0f, depth = 0.0f, s = 0.0f;
+    if (valid) {
+      float gx, gy;
+      project_pixel(cm[v], wx, wy, wz, px, py, depth);
+      pixel_to_norm(g, px, py, gx, gy);
+      const Taps t = bilinear_taps(gx, gy, g.W, g.H);
+      if (t.inside) {
+        const float* cl = frame + v * view_stride + j;
+        float h[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h[k] = ((t.inside >> k) & 1) ? cl[size_t(t.off[k]) * JP] : 0.0f;
+        s = __fmul_rn(h[0], t.w[0]);
+#pragma unroll
+        for (int k = 1; k < 4; ++k) s = __fmaf_rn(h[k], t.w[k], s);
+      }
+    }
+    acc = (v == 0) ? s : __fadd_rn(acc, s);
+    if (views)
+      reinterpret_cast<float4*>(views)[((size_t(b) * g.V + v) * N + n) * J + j] = make_float4(px, py, depth, s);
+  }
+  if (conf) conf[i] = clampf(__fdiv_rn(acc, float(g.V)), 0.0f, 1.0f);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Whole-space cubes (+ fused z-max).  A workgroup owns CPB = 256/Z complete z-columns so the
 // z-max never leaves the workgroup: values go through LDS [JP][256] and CPB*J threads each
 // reduce one column of one joint.
@@ -707,6 +755,19 @@ extern "C" int fvp_project_whole(const float* heat_cl, const float* cams, const 
                      reinterpret_cast<const Cam*>(cams), frame_set, ax, ay, az, X, Y, Z, *g, cubes, zmax);
   FVP_NV_SWITCH(g->JP / 4, CALL)
 #undef CALL
+  return launch_status();
+}
+
+extern "C" int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* frame_set,
+                                  const float* fused_poses, int B, int N, const FvpGeom* g, float* views,
+                                  float* joint_conf, fvp_stream_t s) {
+  FVP_REQUIRE(heat_cl && cams && frame_set && fused_poses && (views || joint_conf) && B >= 0 && N >= 0);
+  if (int e = check_geom(g)) return e;
+  FVP_LIMIT(size_t(B) * N * g->J * g->V < (size_t(1) << 29));   // item and element indices stay inside int32
+  if (B == 0 || N == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_joint_evidence, dim3(ceil_div(B * N * g->J, 256)), dim3(256), 0, as_stream(s), heat_cl,
+                     reinterpret_cast<const Cam*>(cams), frame_set, fused_poses, B, N, *g, views, joint_conf);
   return launch_status();
 }
 

@@ -525,3 +525,27 @@ class HotPath:
         self.last_jln = dict(planes=planes, feat=feat, boxes=boxes, offset=offset, pose2d=pose2d, pmax=pmax, wgt=wgt,
                              valid=valid)
         return fused5, plane_poses
+
+    def joint_evidence(self, fused_poses, heatmaps, meta, cameras, resize_transform, reuse_staging=False):
+        """Per-view reprojection and heatmap support of every joint of ``fused_poses`` [B,N,J,5] (fvp_joint_evidence):
+        returns ``views`` [B,V,N,J,4] = (px, py, depth, sample) and ``joint_conf`` [B,N,J] = the clamped view mean of the
+        samples - the value the whole-space projection puts into a voxel centred on the joint (project_whole.py:83,86),
+        bit for bit.  One launch, no host synchronisation; slots with ``fused_poses[b,n,0,3] < 0`` come back as zeros."""
+        self._check_tensor(fused_poses, "fused_poses")
+        if fused_poses.dim() != 4 or fused_poses.shape[2:] != (self.J, 5) or fused_poses.shape[0] != heatmaps.shape[0] \
+                or not fused_poses.is_contiguous():
+            raise capi.FvpError(f"fused_poses must be contiguous [B,N,J,5] with B = {heatmaps.shape[0]}, J = {self.J}, "
+                                f"got {tuple(fused_poses.shape)}")
+        B, N = fused_poses.shape[:2]
+        V = heatmaps.shape[1]
+        g = self.geom(resize_transform)
+        g.V = V
+        fs = self.frame_sets(meta, cameras, V)
+        hcl = self.heat_cl(heatmaps, g, reuse=reuse_staging)
+        views = torch.empty((B, V, N, self.J, 4), device=self.device)
+        joint_conf = torch.empty((B, N, self.J), device=self.device)
+        if B * N == 0:
+            return views, joint_conf                    # both empty (an empty tensor has no address to pass)
+        self._call("fvp_joint_evidence", _ptr(hcl), _ptr(self.geo.cams), _ptr(fs), _ptr(fused_poses), B, N, C.byref(g),
+                   _ptr(views), _ptr(joint_conf), self.stream())
+        return views, joint_conf

@@ -4,6 +4,10 @@
 ``forward(backbone=None, views=None, meta=None, targets=None, input_heatmaps=None,
 cameras=None, resize_transform=None)`` returns
 ``(fused_poses [B,N,J,5], plane_poses [3,B,N,J,2], proposal_centers [B,N,7], input_heatmaps, None)``.
+
+Beyond the reference: ``model.evidence = True`` makes ``forward`` also leave ``model.last_evidence = (views [B,V,N,J,4],
+joint_conf [B,N,J])`` - every fused joint reprojected into every camera image with its heatmap support there, and the
+per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``).
 """
 import time
 
@@ -31,7 +35,25 @@ class FasterVoxelPoseNet(nn.Module):
         self.lambda_loss_1d = cfg.TRAIN.LAMBDA_LOSS_1D
         self.lambda_loss_bbox = cfg.TRAIN.LAMBDA_LOSS_BBOX
         self.lambda_loss_fused = cfg.TRAIN.LAMBDA_LOSS_FUSED
+        # True: forward() also evaluates joint_evidence() on its own poses (one more launch) and keeps the pair in
+        # `last_evidence`; the returned tuple is the same either way
+        self.evidence = False
+        self.last_evidence = None
         self.eval()
+
+    def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
+        """Per-joint, per-view evidence for ANY poses in the layout of ``fused_poses`` [B,N,J,5] (the model's own, a
+        tracker's smoothed ones, ground truth) against ``input_heatmaps`` [B,V,J,H,W]:
+
+        ``views`` [B,V,N,J,4] = (px, py, depth, s): the joint's distorted pixel in the original image of camera v (before
+        any clamp; it may lie outside the image), its camera-space depth (<= 0: behind the camera), and the bilinear
+        sample s of the joint's own heatmap of that view at the position the projection layers sample;
+        ``joint_conf`` [B,N,J] = clamp(mean over views of s, 0, 1): the value the reference's whole-space projection
+        (project_whole.py:83,86) puts into a voxel centred on the joint, bit for bit.
+
+        Slots with ``fused_poses[b,n,0,3] < 0`` are all zero.  One static-shape launch on the current stream, no host
+        synchronisation."""
+        return self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform)
 
     def forward(self, backbone=None, views=None, meta=None, targets=None, input_heatmaps=None, cameras=None,
                 resize_transform=None):
@@ -90,6 +112,11 @@ class FasterVoxelPoseNet(nn.Module):
         mask = self.engine.last["valid"]              # uint8 [B,N] = proposal_centers[:, :, 3] >= 0 (:45), written by fvp_proposals
         fused_poses, plane_poses = self.joint_net.forward5(meta, input_heatmaps, proposal_centers, mask, cameras,
                                                            resize_transform, _reuse_staging=True)
+        if self.evidence:
+            # static-shape and sync-free like the rest of the forward: under GraphedForward / GraphedPipeline the launch is
+            # part of the captured graph and `last_evidence` holds static tensors, overwritten by the next replay
+            self.last_evidence = self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform,
+                                                            reuse_staging=True)
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -157,6 +184,7 @@ class PipelinedForward:
             m = FasterVoxelPoseNet(model.cfg).to(model.device)
             m.load_state_dict(model.state_dict())
             m.eval()
+            m.evidence = model.evidence
             # camera tables and the per-sequence coordinate cache (164 MB for the Panoptic shape set) are read-only
             # between rebuilds: one copy for all replicas (engine.SharedGeometry orders the streams behind a rebuild)
             m.engine.geo = model.engine.geo

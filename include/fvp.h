@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 10
+#define FVP_ABI_VERSION 11
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -92,6 +92,27 @@ int fvp_project_whole(const float* heat_cl, const float* cams, const int32_t* fr
 int fvp_project_columns(const float* heat_cl, const float* cams, const int32_t* frame_set, const float* ax,
                         const float* ay, const float* az, int X, int Y, int Z, int B, const FvpGeom* g,
                         const int64_t* flat, int N, float* feat1d, fvp_stream_t s);
+
+/* ---- joint evidence (ABI 11): per-view reprojection and heatmap support of every fused joint ----------
+ * For frame b, person slot n, joint j, view v, with (x,y,z) = fused_poses[b][n][j][0:3] (fused_poses = [B][N][J][5],
+ * the output of fvp_fuse_poses, or any poses in that layout: a tracker's, ground truth):
+ *   views[b][v][n][j] = (px, py, depth, s_v)                                        views = [B][V][N][J][4]
+ *     (px, py)  the distorted pixel in the ORIGINAL camera image, cameras.project_point (utils/cameras.py:30-56),
+ *               BEFORE the [-1, clamp_max] clamp of project_whole.py:51 (it may lie outside the image);
+ *     depth     the camera-space z, xcam[2] of cameras.py:43, before the + 1e-5 of :44 (<= 0: behind the camera);
+ *     s_v       the bilinear sample of channel j of heat_cl[b][v] at the sampling coordinate of that point
+ *               (project_whole.py:49-60: clamp, resize transform, heatmap scale, clamp +-1.1), i.e. what
+ *               F.grid_sample(align_corners=True, zero padding) of :83 returns for that channel; 0 when no tap is inside;
+ *   joint_conf[b][n][j] = clamp01((s_0 + s_1 + ... + s_{V-1}) / V)                  joint_conf = [B][N][J]
+ *     summed in view order, every operation rounded on its own: the value project_whole.py:83,86 would put into
+ *     channel j of a voxel centred on the joint.
+ * Same device functions as the projection kernels: s_v and joint_conf are bit-equal to what fvp_project_whole writes
+ * for a voxel centre at that position.  A slot is valid when fused_poses[b][n][0][3] >= 0 (the flag fvp_fuse_poses
+ * copies from proposal_centers[...][3]); every output element of an invalid slot is written as 0.  Every element of
+ * both outputs is written.  Either output may be NULL (not both).  cams / frame_set / g as for fvp_project_whole. */
+int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* frame_set,
+                       const float* fused_poses, int B, int N, const FvpGeom* g,
+                       float* views /* [B,V,N,J,4] */, float* joint_conf /* [B,N,J] */, fvp_stream_t s);
 
 /* z-max of already materialised cubes [n][Z] -> [n] (n = B*J*X*Y): the first statement of
  * CenterNet.forward (cnns_2d.py:174) when it is called on its own. */

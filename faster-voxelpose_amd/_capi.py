@@ -9,12 +9,14 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 11           # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 12           # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
 FVP_MAX_VIEWS = 8
 FVP_MAX_JOINTS = 32
+FVP_TRACK_MAX_DETS = 32
+FVP_TRACK_MAX_TRACKS = 64
 
 OP_CONV, OP_POOL2, OP_CONVT2 = 0, 1, 2
 EPI_RELU, EPI_RES, EPI_RES_AFTER_RELU = 1, 2, 4
@@ -60,6 +62,7 @@ SIGNATURES = {
     "fvp_project_whole": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _G, _P, _P, _P],
     "fvp_project_columns": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _G, _P, _I, _P, _P],
     "fvp_joint_evidence": [_P, _P, _P, _P, _I, _I, _G, _P, _P, _P],
+    "fvp_track_update": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "fvp_zmax": [_P, _P, C.c_long, _I, _P],
     "fvp_person_boxes": [_P, _I, _P, _P, _P, _P, _P],
     "fvp_project_individual": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _G, _P, _P],

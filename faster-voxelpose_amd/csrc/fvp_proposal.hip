@@ -176,6 +176,184 @@ k_proposal_layer(const long long* __restrict__ topk_index, const float* __restri
   c[6] = match_bbox[size_t(i) * 2 + 1];
 }
 
+// ---- pose tracker (ABI 12): person identities across the frames of a camera sequence -----------------------------
+// No reference counterpart (the reference returns a bag of poses per frame); the definition is in include/fvp.h.
+// One workgroup of one wave per sequence.  Lane t owns track slot t (id and age in registers, T <= 64); the track poses,
+// the frame's detections and the N x T cost matrix live in LDS.  The wave walks the batch's frames in order and skips the
+// frames of other sequences, so a batch is one launch whatever B is; the state is read once at entry and written back
+// once at exit.  Latency-bound like k_proposals (B * N * T * J distances, ~19 000 at the headline shape): nothing is tuned.
+// The sets every lane needs (valid detections, live / matched tracks, matched detections) are wave-uniform bit masks.
+// The strided loops are kept rolled (#pragma unroll 1): unrolled eight times with their remainder loops they cost 16 SGPR
+// spills for loop-invariant predicates and buy nothing in a kernel that waits on one LDS read after another.
+constexpr int kTrackDets = FVP_TRACK_MAX_DETS, kTrackSlots = FVP_TRACK_MAX_TRACKS;
+static_assert(kTrackDets <= 32 && kTrackSlots <= 64, "masks: 32 detections, one lane per track slot");
+
+__device__ __forceinline__ unsigned wave_or(unsigned v) {
+  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+  return v;
+}
+
+__global__ void __launch_bounds__(64)
+k_track_update(const float* __restrict__ poses, const int* __restrict__ frame_set, float* __restrict__ trk_pose,
+               int* __restrict__ trk_id, int* __restrict__ trk_age, int* __restrict__ next_id, int* __restrict__ ids,
+               int* __restrict__ slots, float* __restrict__ costs, int B, int N, int J, int nseq, int T, float gate,
+               int max_age) {
+  __shared__ float s_trk[kTrackSlots * FVP_MAX_JOINTS * 3];    // [T][J][3]
+  __shared__ float s_det[kTrackDets * FVP_MAX_JOINTS * 3];     // [N][J][3] of the current frame
+  __shared__ unsigned s_cost[kTrackDets * kTrackSlots];        // cost bits of entry n * T + t, ~0u = not eligible
+  __shared__ int s_slot[kTrackDets], s_id[kTrackDets];         // per detection of the current frame
+  __shared__ unsigned s_mcost[kTrackDets];
+  const int s = blockIdx.x, lane = threadIdx.x, J3 = J * 3;
+  const bool slot_lane = lane < T;
+  int id = -1, age = 0;
+  if (slot_lane) {
+    id = trk_id[size_t(s) * T + lane];
+    age = trk_age[size_t(s) * T + lane];
+  }
+  int next = next_id[s];
+#pragma unroll 1
+  for (int i = lane; i < T * J3; i += 64) s_trk[i] = trk_pose[size_t(s) * T * J3 + i];
+  // entry e = n * T + t; this lane's entries are e = lane + 64 k: (n, t) advance by (q64, r64) with one carry
+  const int n0 = lane / T, t0 = lane - n0 * T, q64 = 64 / T, r64 = 64 - q64 * T;
+  const float fJ = float(J);
+
+#pragma unroll 1
+  for (int b = 0; b < B; ++b) {
+    const int fs = frame_set ? frame_set[b] : 0;
+    if (fs != s) {
+      // a frame of no sequence of this tracker: nobody owns it, workgroup 0 writes it as all invalid
+      if (s == 0 && (fs < 0 || fs >= nseq) && lane < N) {
+        ids[size_t(b) * N + lane] = -1;
+        slots[size_t(b) * N + lane] = -1;
+        costs[size_t(b) * N + lane] = -1.0f;
+      }
+      continue;
+    }
+    __syncthreads();                            // the previous frame's readers of s_det / s_slot are done
+    const float* fp = poses + size_t(b) * N * J * 5;
+#pragma unroll 1
+    for (int i = lane; i < N * J; i += 64) {
+      s_det[i * 3 + 0] = fp[size_t(i) * 5 + 0];
+      s_det[i * 3 + 1] = fp[size_t(i) * 5 + 1];
+      s_det[i * 3 + 2] = fp[size_t(i) * 5 + 2];
+    }
+    bool valid = false;
+    if (lane < N) {
+      valid = fp[size_t(lane) * J * 5 + 3] >= 0.0f;
+      s_slot[lane] = -1;
+    }
+    const unsigned dets = wave_or(valid ? 1u << (lane & 31) : 0u);
+    const bool live = slot_lane && id >= 0;
+    const unsigned live_lo = wave_or(live && lane < 32 ? 1u << lane : 0u);
+    const unsigned live_hi = wave_or(live && lane >= 32 ? 1u << (lane - 32) : 0u);
+    const unsigned long long tracks = (unsigned long long)live_hi << 32 | live_lo;
+    __syncthreads();
+
+    // cost(n, t) = (d_0 + d_1 + ... + d_{J-1}) / J, every operation rounded on its own
+#pragma unroll 1
+    for (int e = lane, n = n0, t = t0; e < N * T; e += 64) {
+      unsigned bits = ~0u;
+      if ((dets >> n & 1u) && (tracks >> t & 1ull)) {
+        const float* d = s_det + n * J3;
+        const float* p = s_trk + t * J3;
+        float sum = 0.0f;
+#pragma unroll 1
+        for (int j = 0; j < J; ++j) {
+          const float dx = __fsub_rn(d[3 * j], p[3 * j]), dy = __fsub_rn(d[3 * j + 1], p[3 * j + 1]),
+                      dz = __fsub_rn(d[3 * j + 2], p[3 * j + 2]);
+          const float dj = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+          sum = j == 0 ? dj : __fadd_rn(sum, dj);
+        }
+        const float cost = __fdiv_rn(sum, fJ);
+        if (cost <= gate) bits = unsigned(__float_as_int(cost));      // (a NaN cost is never eligible)
+      }
+      s_cost[e] = bits;                         // read back by this lane only
+      n += q64;
+      t += r64;
+      if (t >= T) { t -= T; ++n; }
+    }
+
+    // greedy assignment: the smallest (cost, n, t) among unassigned pairs, as the 64-bit key cost bits : n * T + t
+    unsigned matched_d = 0;
+    unsigned long long matched_t = 0;
+    for (;;) {
+      unsigned bc = ~0u, be = ~0u;
+#pragma unroll 1
+      for (int e = lane, n = n0, t = t0; e < N * T; e += 64) {
+        const unsigned c = s_cost[e];
+        if (c < bc && !(matched_d >> n & 1u) && !(matched_t >> t & 1ull)) { bc = c; be = unsigned(e); }   // (e ascends)
+        n += q64;
+        t += r64;
+        if (t >= T) { t -= T; ++n; }
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned oc = __shfl_xor(bc, o), oe = __shfl_xor(be, o);
+        if (oc < bc || (oc == bc && oe < be)) { bc = oc; be = oe; }
+      }
+      if (bc == ~0u) break;                     // wave-uniform
+      const int n = int(be) / T, t = int(be) - n * T;
+      matched_d |= 1u << n;
+      matched_t |= 1ull << t;
+      if (lane == t) {
+        s_id[n] = id;
+        s_slot[n] = t;
+        s_mcost[n] = bc;
+        age = 0;
+      }
+    }
+
+    // unmatched live tracks age; past max_age the slot is free again, for this very frame's births
+    if (live && !(matched_t >> lane & 1ull)) {
+      ++age;
+      if (age > max_age) id = -1;
+    }
+    // births in ascending n: the lowest free slot, else the live track of largest age (lowest slot on a tie).  T >= N: a
+    // full table holds a track that was neither matched nor born in this frame, so the evicted one has age >= 1.
+    const unsigned births = dets & ~matched_d;
+#pragma unroll 1
+    for (int n = 0; n < N; ++n) {
+      if (!(births >> n & 1u)) continue;        // wave-uniform
+      int ka = slot_lane ? (id < 0 ? int(0x80000000u) : -age) : 0x7fffffff, kl = lane;
+      for (int o = 32; o > 0; o >>= 1) {
+        const int oa = __shfl_xor(ka, o), ol = __shfl_xor(kl, o);
+        if (oa < ka || (oa == ka && ol < kl)) { ka = oa; kl = ol; }
+      }
+      if (lane == kl) {
+        id = next;
+        age = 0;
+        s_id[n] = next;
+        s_slot[n] = kl;
+        s_mcost[n] = unsigned(__float_as_int(-1.0f));
+      }
+      ++next;
+    }
+    __syncthreads();
+
+    if (lane < N) {
+      ids[size_t(b) * N + lane] = valid ? s_id[lane] : -1;
+      slots[size_t(b) * N + lane] = valid ? s_slot[lane] : -1;
+      costs[size_t(b) * N + lane] = valid ? __int_as_float(int(s_mcost[lane])) : -1.0f;
+    }
+    // every valid detection has a slot now (matched or born): its pose becomes the track's
+#pragma unroll 1
+    for (int n = 0; n < N; ++n) {
+      const int t = s_slot[n];
+      if (t < 0) continue;
+#pragma unroll 1
+      for (int r = lane; r < J3; r += 64) s_trk[t * J3 + r] = s_det[n * J3 + r];
+    }
+  }
+
+  __syncthreads();
+  if (slot_lane) {
+    trk_id[size_t(s) * T + lane] = id;
+    trk_age[size_t(s) * T + lane] = age;
+  }
+  if (lane == 0) next_id[s] = next;
+#pragma unroll 1
+  for (int i = lane; i < T * J3; i += 64) trk_pose[size_t(s) * T * J3 + i] = s_trk[i];
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -230,5 +408,18 @@ extern "C" int fvp_proposal_layer(const int64_t* topk_index, const float* topk_c
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_proposal_layer, dim3(ceil_div(B * N, 64)), dim3(64), 0, as_stream(s),
                      reinterpret_cast<const long long*>(topk_index), topk_confs, match_bbox, sb, min_score, B * N, centers);
+  return launch_status();
+}
+
+extern "C" int fvp_track_update(const float* fused_poses, const int32_t* frame_set, float* trk_pose, int32_t* trk_id,
+                                int32_t* trk_age, int32_t* next_id, int32_t* ids, int32_t* slots, float* costs, int B,
+                                int N, int J, int nseq, int T, float gate_mm, int max_age, fvp_stream_t s) {
+  FVP_REQUIRE(fused_poses && trk_pose && trk_id && trk_age && next_id && ids && slots && costs);
+  FVP_REQUIRE(B >= 0 && N > 0 && J > 0 && nseq > 0 && T >= N && max_age >= 0);
+  FVP_LIMIT(N <= kTrackDets && T <= kTrackSlots && J <= FVP_MAX_JOINTS);
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_track_update, dim3(nseq), dim3(64), 0, as_stream(s), fused_poses, frame_set, trk_pose, trk_id,
+                     trk_age, next_id, ids, slots, costs, B, N, J, nseq, T, gate_mm, max_age);
   return launch_status();
 }

@@ -7,7 +7,9 @@ cameras=None, resize_transform=None)`` returns
 
 Beyond the reference: ``model.evidence = True`` makes ``forward`` also leave ``model.last_evidence = (views [B,V,N,J,4],
 joint_conf [B,N,J])`` - every fused joint reprojected into every camera image with its heatmap support there, and the
-per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``).
+per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``).  ``model.tracker = PoseTracker(cfg)``
+(core/tracking.py) makes ``forward`` also leave ``model.last_tracks = (ids [B,N], slots [B,N], costs [B,N])`` - one
+identity per person across the frames of a camera sequence, one more launch, no host synchronisation.
 """
 import time
 
@@ -39,6 +41,11 @@ class FasterVoxelPoseNet(nn.Module):
         # `last_evidence`; the returned tuple is the same either way
         self.evidence = False
         self.last_evidence = None
+        # a core.tracking.PoseTracker: forward() also calls tracker.update() on its own fused_poses (one more launch on the
+        # current stream, frames in batch order) and keeps (ids, slots, costs) in `last_tracks`; the returned tuple is the
+        # same either way.  None: the forward issues exactly the launches it issues without the feature.
+        self.tracker = None
+        self.last_tracks = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -117,6 +124,14 @@ class FasterVoxelPoseNet(nn.Module):
             # part of the captured graph and `last_evidence` holds static tensors, overwritten by the next replay
             self.last_evidence = self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform,
                                                             reuse_staging=True)
+        if self.tracker is not None:
+            # the frames' sequence rows are the engine's own table (frame_sets: cached, no upload here); static-shape and
+            # sync-free, so a captured graph holds the launch and the state in device memory carries from replay to replay
+            if len(self.engine.geo.seq_ids) > self.tracker.nseq:
+                raise capi.FvpError(f"the engine has seen {len(self.engine.geo.seq_ids)} sequences, model.tracker was "
+                                    f"built for nseq = {self.tracker.nseq}")
+            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
+            self.last_tracks = self.tracker.update(fused_poses, sequences=fs)
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -129,7 +144,11 @@ class GraphedForward:
     The path has no host synchronisation and only static-shape launches, so one capture covers
     staging, HDN, JLN and fusion (~110 kernels); a replay costs one host call instead of ~110
     ctypes launches.  Inputs are copied into a static buffer; outputs are the graph's static
-    tensors (clone them if they must outlive the next replay)."""
+    tensors (clone them if they must outlive the next replay).
+
+    With ``model.tracker`` set the tracker's launch is part of the graph and ``model.last_tracks`` holds static tensors;
+    the track state lives in device memory, so it carries from replay to replay.  The warm-up and capture runs of the
+    constructor are forwards like any other and advance that state: call ``model.tracker.reset()`` after construction."""
 
     def __init__(self, model, meta, input_heatmaps, cameras, resize_transform, warmup=2):
         self.model = model
@@ -165,7 +184,12 @@ class PipelinedForward:
 
     ``submit`` returns ``(outputs, event)``; the outputs are valid for a consumer stream after
     ``event.wait()`` (or after ``synchronize()``).  Results are identical to the plain forward:
-    every kernel is deterministic and replicas share nothing but read-only inputs."""
+    every kernel is deterministic and replicas share nothing but read-only inputs.
+
+    Batches run on several streams and replicas, and a tracker needs the frames in time order on one stream: the
+    pipeline takes no ``model.tracker`` (the constructor refuses a model that has one).  Keep the ``PoseTracker`` beside
+    the pipeline and call ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after
+    ``event.wait()``."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -178,6 +202,9 @@ class PipelinedForward:
         the host time spent in that wait."""
         assert depth >= 1
         assert streams is None or len(streams) >= depth
+        if model.tracker is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.tracker = None "
+                                "and call tracker.update(outputs[0], meta) on the consumer stream in submit order")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):
@@ -238,7 +265,9 @@ class GraphedPipeline:
     the outputs are the slot's static tensors, overwritten when the slot comes round again (``depth`` submits later): read
     or clone them before that.  Same kernels, same order per slot: results equal ``PipelinedForward`` bit for bit.
     Shapes, cameras and the sequence list are fixed at capture time (the reference's caller loop, function.py:136-148,
-    feeds one sequence mix per run); a different shape needs a new pipeline."""
+    feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, a tracker
+    stays outside: ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after ``event.wait()``
+    (before the slot comes round again)."""
 
     def __init__(self, model, depth, meta, input_heatmaps, cameras, resize_transform, streams=None, warmup=2):
         self.pipe = PipelinedForward(model, depth=depth, streams=streams)

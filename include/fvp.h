@@ -26,10 +26,12 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 11
+#define FVP_ABI_VERSION 12
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
+#define FVP_TRACK_MAX_DETS 32   /* fvp_track_update: person slots per frame (N)   */
+#define FVP_TRACK_MAX_TRACKS 64 /* fvp_track_update: track slots per sequence (T) */
 
 #define FVP_EINVAL 10001 /* bad argument (null pointer, unsupported size) */
 #define FVP_ELIMIT 10002 /* size beyond a compiled limit (see message) */
@@ -113,6 +115,40 @@ int fvp_project_columns(const float* heat_cl, const float* cams, const int32_t* 
 int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* frame_set,
                        const float* fused_poses, int B, int N, const FvpGeom* g,
                        float* views /* [B,V,N,J,4] */, float* joint_conf /* [B,N,J] */, fvp_stream_t s);
+
+/* ---- pose tracker (ABI 12): one identity per person across the frames of a camera sequence -----------------------
+ * No reference counterpart: the reference returns a bag of poses per frame, ordered by NMS rank.  This call gives every
+ * valid slot of fused_poses [B][N][J][5] a track id that follows the person from frame to frame, on the device, in one
+ * launch per batch and without host synchronisation.  Nearest-pose greedy association only: no motion prediction, no
+ * pose smoothing, no re-identification after max_age, no optimal (Hungarian) assignment.
+ * State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
+ *   trk_pose [nseq][T][J][3] fp32, trk_id [nseq][T] int32 (-1 = free slot), trk_age [nseq][T] int32, next_id [nseq] int32;
+ *   the initial state is all ids -1, all ages 0, next_id 0 (the poses of free slots are never read).
+ * frame_set [B] int32 (may be NULL = every frame belongs to sequence 0): the sequence of each frame, the table the
+ * projection calls take.  Frames are consumed in batch order; the frames of one sequence are its time line; sequences are
+ * independent.  For frame b of sequence s:
+ *   1. detections D = slots n with fused_poses[b][n][0][3] >= 0; live tracks A = slots t with trk_id[s][t] >= 0;
+ *   2. cost(n,t) = (d_0 + d_1 + ... + d_{J-1}) / J,  d_j = sqrt(dx*dx + dy*dy + dz*dz) between joint j of the detection
+ *      and of the track (mm); fp32, every operation rounded on its own, sums left to right as written;
+ *   3. a pair is eligible when cost <= gate_mm (a NaN cost never is); greedy: repeatedly the eligible pair of an
+ *      unassigned detection and an unassigned track with the smallest (cost, n, t) in lexicographic order;
+ *   4. matched (n,t): trk_pose[s][t] = the detection's xyz, trk_age[s][t] = 0;
+ *      ids[b][n] = trk_id[s][t], slots[b][n] = t, costs[b][n] = cost(n,t);
+ *   5. unmatched live track: trk_age += 1; if it is now > max_age, trk_id = -1 (the slot may be reused in this frame);
+ *   6. unmatched detections in ascending n: the lowest free slot, or, when none is free, the live track with the largest
+ *      age (lowest slot on a tie; T >= N, so its age is >= 1) is evicted; the slot gets trk_id = next_id[s]
+ *      (then next_id[s] += 1), trk_age = 0 and the detection's xyz; ids[b][n] = the new id, slots[b][n] = the slot,
+ *      costs[b][n] = -1;
+ *   7. invalid slots: ids = slots = -1, costs = -1.
+ * ids, slots [B][N] int32 and costs [B][N] fp32: every element is written by every call.  A frame whose frame_set entry
+ * is outside [0, nseq) belongs to no sequence: its outputs are written as invalid and no state changes.
+ * One workgroup of one wave per sequence walks the batch.  FVP_EINVAL: a null pointer (frame_set excepted), N, J or nseq
+ * < 1, T < N, max_age < 0;  FVP_ELIMIT: N > FVP_TRACK_MAX_DETS, T > FVP_TRACK_MAX_TRACKS, J > FVP_MAX_JOINTS.  Nothing is
+ * written when an error is returned.  B == 0 returns 0 without a launch. */
+int fvp_track_update(const float* fused_poses, const int32_t* frame_set, float* trk_pose, int32_t* trk_id,
+                     int32_t* trk_age, int32_t* next_id, int32_t* ids /* [B,N] */, int32_t* slots /* [B,N] */,
+                     float* costs /* [B,N] */, int B, int N, int J, int nseq, int T, float gate_mm, int max_age,
+                     fvp_stream_t s);
 
 /* z-max of already materialised cubes [n][Z] -> [n] (n = B*J*X*Y): the first statement of
  * CenterNet.forward (cnns_2d.py:174) when it is called on its own. */

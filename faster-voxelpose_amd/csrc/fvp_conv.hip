@@ -941,6 +941,28 @@ k_pack_tpair(const float* __restrict__ w, int cin, int cout, int cinp, int coutp
   dst[i] = (co < cout && ci < cin) ? w[((size_t(ci) * cout + co) * 2 + dy) * 2 + dx] : 0.0f;
 }
 
+// ---- host side: diagnostics switches, routing (conv_form), tile / chunk planner, one launch function per form ----
+// Diagnostics switches (FVP_* environment variables, honoured by the diagnostics build only: the product compiles
+// env_size() to its default).
+static const size_t kLdsBudget = env_size("FVP_CONV_LDS_KB", 64) * 1024;   // LDS the chunk plan of k_conv / k_conv_dma may fill
+static const int kAblate = int(env_size("FVP_CONV_ABLATE", 0));           // ConvArgs::ablate mask (skip staging / MFMA loop / stores)
+static const int kForcePB = int(env_size("FVP_CONV_PB", 0));              // force the pixel blocks per wave of k_conv / k_conv_dma
+static const int kNoDma = int(env_size("FVP_CONV_NO_DMA", 0));            // k_conv (staging through registers) instead of k_conv_dma
+static const int kNoWino = int(env_size("FVP_CONV_NO_WINO", 0));          // 3x3 convs on k_conv_dma instead of the Winograd kernel
+static const int kNoPair = int(env_size("FVP_CONV_NO_PAIR", 0));          // no paired weight layouts (pixel-pair 7x7, paired transposed conv)
+static const int kNoK7 = int(env_size("FVP_CONV_NO_K7", 0));              // 7x7 convs on the pixel-pair form of k_conv_dma
+static const size_t kK7LdsPad = env_size("FVP_K7_LDS_KB", 0) * 1024;      // pad k_conv7's LDS request (fewer workgroups per CU)
+static const int kNoPoolFuse = int(env_size("FVP_CONV_NO_POOL_FUSE", 0)); // the max-pool behind a Winograd conv as its own launch
+static const int kNoHeadFuse = int(env_size("FVP_CONV_NO_HEAD_FUSE", 0)); // the 1x1 conv behind a paired transposed conv as its own launch
+static const int kNoReg = int(env_size("FVP_CONV_NO_REG", 0));            // 1x1 / transposed convs on k_conv_dma
+static const int kRegWgs = int(env_size("FVP_CONV_REG_WGS", 0));          // k_conv_reg: workgroups per CU
+static const int kNoKSplit = int(env_size("FVP_CONV_NO_KSPLIT", 0));      // no split-K form for the small-map 3x3 layers
+// FVP_CONV_REG_MIN_TILES: least number of 32-pixel tiles at which k_conv_reg takes an op
+// (read per call in the diagnostics build, so that a test can run the same stack through both kernels; a constant in the product)
+// Transposed convs gain from 200 tiles on (B = 1: 128 -> 64 22.6 -> 18.6 us at 240 tiles, 64 -> 32 17.2 -> 12.5 us at 960; CenterNet at
+// B = 8: 16.3 -> 9.0 us at 400), 1x1 convs only from ~1 000 (64 -> 128 at 240 tiles: 7.4 -> 13.1 us).
+static long reg_min_tiles(bool transposed) { return long(env_size("FVP_CONV_REG_MIN_TILES", transposed ? 200 : 1024)); }
+
 template <int KH, int KW, int CB, int PB>
 static int launch_conv(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   if (a.dma) {
@@ -975,24 +997,6 @@ static int dispatch_conv(int kh, int kw, int CB, int PB, const ConvArgs& a, dim3
   return FVP_ELIMIT;
 }
 
-// tuning knobs (diagnostics): FVP_CONV_LDS_KB, FVP_CONV_ABLATE, FVP_CONV_PB
-static const size_t kLdsBudget = env_size("FVP_CONV_LDS_KB", 64) * 1024;
-static const int kAblate = int(env_size("FVP_CONV_ABLATE", 0));
-static const int kForcePB = int(env_size("FVP_CONV_PB", 0));
-static const int kNoDma = int(env_size("FVP_CONV_NO_DMA", 0));
-
-static const int kNoWino = int(env_size("FVP_CONV_NO_WINO", 0));
-static const int kNoPair = int(env_size("FVP_CONV_NO_PAIR", 0));
-static const int kNoK7 = int(env_size("FVP_CONV_NO_K7", 0));        // diagnostics: 7x7 convs on the pixel-pair form of k_conv_dma
-static const size_t kK7LdsPad = env_size("FVP_K7_LDS_KB", 0) * 1024;  // diagnostics: pad k_conv7's LDS request (fewer workgroups per CU)
-static const int kNoPoolFuse = int(env_size("FVP_CONV_NO_POOL_FUSE", 0));
-static const int kNoHeadFuse = int(env_size("FVP_CONV_NO_HEAD_FUSE", 0));
-static const int kNoReg = int(env_size("FVP_CONV_NO_REG", 0));     // diagnostics: 1x1 / transposed convs on k_conv_dma
-// (read per call in the diagnostics build, so that a test can run the same stack through both kernels; a constant in the product)
-// Transposed convs gain from 200 tiles on (B = 1: 128 -> 64 22.6 -> 18.6 us at 240 tiles, 64 -> 32 17.2 -> 12.5 us at 960; CenterNet at
-// B = 8: 16.3 -> 9.0 us at 400), 1x1 convs only from ~1 000 (64 -> 128 at 240 tiles: 7.4 -> 13.1 us).
-static long reg_min_tiles(bool transposed) { return long(env_size("FVP_CONV_REG_MIN_TILES", transposed ? 200 : 1024)); }
-static const int kNoKSplit = int(env_size("FVP_CONV_NO_KSPLIT", 0));   // diagnostics: no split-K form for the small-map 3x3 layers
 template <int K, int NB, int MODE>
 static int launch_reg(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   static LdsOptIn optin[2];
@@ -1008,262 +1012,141 @@ static int launch_reg(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   return launch_status();
 }
 
-// k_conv_reg (fvp_conv_reg.h) for 1x1 convs and paired transposed convs whose planes are whole 32-pixel tiles and whose
-// weights fit LDS.  Returns -1 when the layer is not of that kind (the caller goes on to k_conv_dma).  The two kernels
-// produce the same bits, so the choice may depend on the amount of work: below reg_min_tiles() tiles (a few planes of
-// CenterNet's maps) the 256-pixel tiles of k_conv_dma spread over more CUs.
-static bool reg_shape_ok(const FvpConvOp& op, int planes, bool tr) {
-  const int hw = op.h * op.w;
-  if (kNoReg || op.cin != op.cinp || op.h <= 1 || hw % 32) return false;
-  if ((op.flags & FVP_EPI_RES) && op.cout % 8) return false;      // (residual rows are read through a uniform row pointer)
-  if (tr && (op.pair_off <= 0 || kNoPair)) return false;
-  return long(planes) * (hw / 32) >= reg_min_tiles(tr);
-}
-// the 64 -> 32 transposed conv with its fused 1x1 head runs on k_conv_reg (whose MFMA head takes up to 32 output channels;
-// k_conv_dma's fma-chain head stops at 16)
-static bool reg_takes_fused_head(const FvpConvOp& op, int planes) {
-  return op.kind == FVP_OP_CONVT2 && op.cinp == 64 && op.coutp == 32 && reg_shape_ok(op, planes, true);
-}
-
-static int plan_and_launch_reg(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s, bool tr) {
-  const int hw = op.h * op.w;
-  if (!reg_shape_ok(op, planes, tr)) return -1;
-  const long tiles = long(planes) * (hw / 32);
-  int mode = 0, NB = op.coutp / 32;
-  a.wrow = op.coutp;
-  if (tr) {
-    mode = a.w2 ? 2 : 1;
-    NB = 2 * op.coutp / 32;
-    a.wts = params + op.pair_off;
-    a.wrow = 2 * op.coutp;
-    a.ntapT = 2;
-    a.tapT_w = 1;
-  } else if (op.kh != 1 || op.kw != 1 || a.w2) {
-    return -1;
-  }
-  const int ny = 1;
-  // instances exist for these (cinp, NB, mode) only; the key is injective on that domain (cinp = 56,
-  // coutp = 2688 used to alias 6440)
-  if (NB < 1 || NB > 4 || (op.cinp != 16 && op.cinp != 32 && op.cinp != 64 && op.cinp != 128)) return -1;
-  // raw-buffer addressing: a plane's input (K rows) and output (cout rows, + 4 for the upper half wave) are addressed with
-  // 32-bit byte offsets and an `int` num_records
-  if (double(op.cinp) * hw * 4.0 >= 2147483648.0 || (double(op.coutp) + 4.0) * hw * (tr ? 4.0 : 1.0) * 4.0 >= 2147483648.0) return -1;
-  const int key = op.cinp * 100 + NB * 10 + mode;
-  if (key != 1610 && key != 3210 && key != 3220 && key != 6440 && key != 12841 && key != 6421 && key != 6422) return -1;
-  a.m_tpp = make_magic(hw / 32);
-  a.m_w = make_magic(op.w);
-  a.zeros = params;
-  a.ablate = kAblate;
-  const size_t lds = (size_t(op.cinp) * 32 * NB + 3 * size_t(op.coutp) + (mode == 2 ? 32 * 32 + 96 : 0)) * sizeof(float);
-  static const int kRegWgs = int(env_size("FVP_CONV_REG_WGS", 0));   // diagnostics: workgroups per CU
-  const int occ = kRegWgs ? kRegWgs : (op.cinp * NB <= 128 ? 3 : 2);
-  const int per_cu = std::max(1, std::min(occ, int((160 * 1024) / (lds + 256))));
-  const int nz = tr ? 2 : 1;
-  const long want = (tiles + 3) / 4;
-  const int gx = int(std::min<long>(want, std::max(1, persistent_workgroups() * per_cu / (nz * ny))));
-  dim3 grid(gx, ny, nz);
-  ProfScope ps(FVP_K_CONV, s, 2.0 * op.cin * op.cout * (tr ? 4.0 : 1.0) * hw * planes, 1, prof_level() >= 2);
-  switch (key) {
-    case 1610: return launch_reg<16, 1, 0>(a, grid, lds, s);
-    case 3210: return launch_reg<32, 1, 0>(a, grid, lds, s);
-    case 3220: return launch_reg<32, 2, 0>(a, grid, lds, s);
-    case 6440: return launch_reg<64, 4, 0>(a, grid, lds, s);
-    case 12841: return launch_reg<128, 4, 1>(a, grid, lds, s);
-    case 6421: return launch_reg<64, 2, 1>(a, grid, lds, s);
-    default: return launch_reg<64, 2, 2>(a, grid, lds, s);
-  }
-}
-
-// ConvTranspose(k2,s2) in the paired form: CB = 2*coutp/32 accumulator blocks (both column taps),
-// grid.z = output row parity.
-static int plan_and_launch_tpair(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s) {
-  const int CB = 2 * op.coutp / 32, PB = 4 / CB;         // (2,2) or (4,1)
-  a.wts = params + op.pair_off;
-  a.wrow = 2 * op.coutp;
-  a.ntapT = 2;
-  a.tapT_w = 1;
-  a.ablate = kAblate;
-  const int hw = op.h * op.w, TP = PB * 128;
-  a.TW = op.w;
-  if (hw <= TP) {
-    a.TH = op.h;
-    a.TN = TP / hw;
-  } else if (op.w <= TP) {
-    a.TH = TP / op.w;
-    a.TN = 1;
-  } else {
-    return FVP_ELIMIT;
-  }
-  a.m_w = make_magic(a.TW);
-  a.m_thw = make_magic(a.TH * a.TW);
-  a.tiles_x = 1;
-  a.tiles_y = ceil_div(op.h, a.TH);
-  a.vec = a.dma = 1;
-  a.zeros = params;
-  const size_t per_ch = (size_t(a.TN) * a.TH * (a.TW + 4) + size_t(32) * CB) * sizeof(float);
-  const size_t epi_bytes = (size_t(3) * op.coutp + 96) * sizeof(float);     // BN vectors (+ the fused 1x1 conv's) in LDS
-  int CC = int((kLdsBudget - 64 - epi_bytes) / (per_ch * 2)) & ~1;
-  if (CC > op.cinp) CC = op.cinp;
-  if (CC < 2) return FVP_ELIMIT;
-  while (CC > 2 && size_t(CC) * a.TN * a.TH * (a.TW / 4 + 1) + 1 > 2048) CC -= 2;
-  for (int d = CC; d >= 2 && d * 2 > CC; d -= 2)
-    if (op.cinp % d == 0) { CC = d; break; }
-  a.CC = CC;
-  a.m_qpr = make_magic(a.TW / 4 + 1);
-  a.m_rpc = make_magic(a.TN * a.TH);
-  a.m_thp = make_magic(a.TH);
-  const size_t lds0 = (std::max<size_t>(16 + 2 * (per_ch * CC + 16), 16 + 16384) + 15) & ~size_t(15);
-  a.epi_off = int(lds0 / sizeof(float));
-  const size_t lds = lds0 + epi_bytes;
-  dim3 grid(a.tiles_y * ceil_div(planes, a.TN), 1, 2);
-  ProfScope ps(FVP_K_CONV, s, 2.0 * op.cin * op.cout * 4.0 * hw * planes, 1, prof_level() >= 2);
-  if (CB == 2)
-    hipLaunchKernelGGL((k_conv_dma<1, 1, 2, 2, false, true>), grid, dim3(256), lds, s, a);
-  else
-    hipLaunchKernelGGL((k_conv_dma<1, 1, 4, 1, false, true>), grid, dim3(256), lds, s, a);
+template <int W, int NCG>
+static int launch_k7(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  static LdsOptIn optin;
+  auto k = &k_conv7<W, NCG>;
+  const size_t lds = std::max(kK7LdsPad, size_t(4 * NCG) * conv7_cs(W, kK7Rows) * sizeof(float));
+  if (int e = lds_opt_in(optin, reinterpret_cast<const void*>(k), lds)) return e;
+  hipLaunchKernelGGL(k, grid, dim3(W / 16 * 64), lds, s, a);
   return launch_status();
 }
 
-// Tile selection: all couts per workgroup (CB = coutp/32), PB so that CB*PB <= 8 accumulator
-// tiles per wave, the tile shaped to cover full image rows where possible.
-static int plan_and_launch(const FvpConvOp& op, const float* params, float* const* bufs, int planes,
-                           const uint8_t* plane_valid, int valid_div, hipStream_t s, float* pool_dst = nullptr,
-                           const FvpConvOp* head = nullptr) {
-  ConvArgs a{};
-  a.pool_dst = pool_dst;
-  if (head) {                                          // (eligibility checked by the caller)
-    a.w2 = params + head->w_off;
-    a.epi2 = params + head->e_off;
-    a.dst2 = bufs[head->dst];
-    a.cout2 = head->cout;
-    a.flags2 = head->flags;
-  }
+// The instances of k_conv_reg: (cinp, NB 32-cout accumulator blocks, MODE 0: 1x1 conv, 1: paired transposed conv,
+// 2: paired transposed conv + fused 1x1 head).  The only list: conv_form() asks it, launch_reg_form() launches from it.
+#define FVP_REG_INSTANCES(X) X(16, 1, 0) X(32, 1, 0) X(32, 2, 0) X(64, 4, 0) X(128, 4, 1) X(64, 2, 1) X(64, 2, 2)
+static int reg_blocks(const FvpConvOp& op, bool tr) { return (tr ? 2 : 1) * op.coutp / 32; }
+static int reg_mode(bool tr, bool has_head) { return tr ? (has_head ? 2 : 1) : 0; }
+
+// k_conv_reg (fvp_conv_reg.h) for 1x1 convs and paired transposed convs whose planes are whole 32-pixel tiles and whose
+// weights fit LDS.  k_conv_reg and k_conv_dma produce the same bits, so the choice may depend on the amount of work: below
+// reg_min_tiles() tiles (a few planes of CenterNet's maps) the 256-pixel tiles of k_conv_dma spread over more CUs.
+// `any_map_size` leaves the 2^31 limits out (fused_head() alone passes it).
+static bool reg_takes(const FvpConvOp& op, int planes, bool has_head, bool any_map_size = false) {
+  const bool tr = op.kind == FVP_OP_CONVT2;
+  const int hw = op.h * op.w;
+  if (!tr && (op.kh != 1 || op.kw != 1 || has_head)) return false;
+  if (kNoReg || op.cin != op.cinp || op.h <= 1 || hw % 32) return false;
+  if ((op.flags & FVP_EPI_RES) && op.cout % 8) return false;      // (residual rows are read through a uniform row pointer)
+  if (tr && (op.pair_off <= 0 || kNoPair)) return false;
+  if (long(planes) * (hw / 32) < reg_min_tiles(tr)) return false;
+  bool instance = false;
+#define FVP_X(K_, NB_, MODE_) instance |= op.cinp == K_ && reg_blocks(op, tr) == NB_ && reg_mode(tr, has_head) == MODE_;
+  FVP_REG_INSTANCES(FVP_X)
+#undef FVP_X
+  // raw-buffer addressing: a plane's input (K rows) and output (cout rows, + 4 for the upper half wave) are addressed with
+  // 32-bit byte offsets and an `int` num_records
+  const bool fits = double(op.cinp) * hw * 4.0 < 2147483648.0 && (double(op.coutp) + 4.0) * hw * (tr ? 4.0 : 1.0) * 4.0 < 2147483648.0;
+  return instance && (fits || any_map_size);
+}
+
+// Which kernel form takes an op: every shape rule, once.  A pure function of the op, the number of planes, whether a
+// pool / a 1x1 head is fused behind it, and the diagnostics switches; plan_and_launch(), the two look-aheads of
+// fvp_conv_stack_run and the Winograd planner's entry check all ask it.
+ConvForm conv_form(const FvpConvOp& op, int planes, bool has_pool_dst, bool has_head) {
   const bool tr = op.kind == FVP_OP_CONVT2;
   const int kh = tr ? 1 : op.kh, kw = tr ? 1 : op.kw;
-  a.src = bufs[op.src];
-  a.dst = bufs[op.dst];
-  a.res = op.res >= 0 ? bufs[op.res] : nullptr;
-  a.wts = params + op.w_off;
-  a.epi = params + op.e_off;
-  a.plane_valid = plane_valid;
-  a.valid_div = valid_div > 0 ? valid_div : 1;
-  a.m_vd = make_magic(a.valid_div);
-  a.planes = planes;
-  a.cin = op.cin;
-  a.cinp = op.cinp;
-  a.cout = op.cout;
-  a.coutp = op.coutp;
-  a.H = op.h;
-  a.W = op.w;
-  a.flags = op.flags;
-  if (tr) {
-    a.osx = 2;
-    a.osy = op.h > 1 ? 2 : 1;
-    a.ntapT = op.h > 1 ? 4 : 2;
-    a.tapT_w = 2;
-  } else {
-    a.osx = a.osy = 1;
-    a.ntapT = 1;
-    a.tapT_w = 1;
-  }
-  a.OH = op.h * a.osy;
-  a.OW = op.w * a.osx;
-  if (double(planes) * std::max(op.cin, op.cout) * a.OH * a.OW >= 2147483648.0) return FVP_ELIMIT;
-  a.wrow = op.coutp;
-  if (tr || (kh == 1 && kw == 1)) {
-    const int rc = plan_and_launch_reg(op, a, params, planes, s, tr);
-    if (rc != -1) return rc;
-  }
-  if (tr && op.h > 1 && op.pair_off > 0 && !kNoPair && op.w % 4 == 0 && (op.coutp == 32 || op.coutp == 64))
-    return plan_and_launch_tpair(op, a, params, planes, s);
-  const int CBfull = op.coutp / 32;
-  if (CBfull != 1 && CBfull != 2 && CBfull != 4) return FVP_ELIMIT;
-  a.ablate = kAblate;
-  if (!tr && op.wino_off > 0 && !kNoWino && op.cin == op.cinp && op.cout % 32 == 0 && op.cout == op.coutp) return wino_plan_and_launch(op, a, params, planes, s);
+  if (reg_takes(op, planes, has_head)) return ConvForm::Reg;
+  // a paired weight copy is packed and the map's rows are whole quads
+  const bool paired = op.pair_off > 0 && !kNoPair && op.w % 4 == 0;
+  // ConvTranspose(k2,s2) in the paired form: both column taps in one accumulator row, 2 * coutp / 32 = 2 or 4 blocks
+  if (tr && paired && op.h > 1 && (op.coutp == 32 || op.coutp == 64)) return ConvForm::TPair;
+  // the forms below keep all couts of a 32-block in one wave: 1, 2 or 4 blocks
+  if (op.coutp / 32 != 1 && op.coutp / 32 != 2 && op.coutp / 32 != 4) return ConvForm::Refused;
+  if (tr) return ConvForm::Direct;                       // 1-D or unpaired transposed conv: one 1x1 conv per tap (grid.z)
+  // Winograd F(2x2,3x3): whole 32-cout blocks only, and no padded channels: the epilogue has no per-cout predicate and its
+  // descriptor spans the plane group, so a block of padding couts (cout = 96, coutp = 128) would be written into the next
+  // plane
+  if (op.wino_off > 0 && !kNoWino && op.cin == op.cinp && op.cout % 32 == 0 && op.cout == op.coutp) return ConvForm::Wino;
   // 7x7 front conv on 16x16x4 tiles (k_conv7): a SHAPE rule (map width, channels), never the number of planes.  Maps of
   // 64 / 128 columns (P2PNet: 30 planes per frame); CenterNet's 80 x 80 map (one plane per frame) stays on the pixel-pair
   // form - 8 planes: 25.9 us there, 28.9-29.9 us here (160 one-tile workgroups of 784 chained MFMAs per wave).
-  if (!tr && kh == 7 && kw == 7 && op.pair_off > 0 && !kNoK7 && op.cout <= 16 && !(op.flags & FVP_EPI_RES) && !pool_dst && !head &&
+  // The last line: 32-bit byte offsets of all 4 * NCG channel slots (channels >= cin must stay out of range, never wrap:
+  // ADVICE round 5)
+  if (kh == 7 && kw == 7 && op.pair_off > 0 && !kNoK7 && op.cout <= 16 && !(op.flags & FVP_EPI_RES) && !has_pool_dst && !has_head &&
       (op.w == 64 || op.w == 128) && op.cin <= 20 && op.h >= 4 &&
-      double(4 * (op.cin <= 16 ? 4 : 5)) * op.h * op.w * 4.0 < 2147483648.0) {   // 32-bit byte offsets of all 4 * NCG channel slots (channels >= cin
-                                                                                 // must stay out of range, never wrap: ADVICE round 5)
-    const int ncg = op.cin <= 16 ? 4 : 5;
-    a.wts = params + op.pair_off + size_t(op.cinp) * 7 * 8 * 32;       // the k-grouped copy behind the pixel-pair copy
-    a.tiles_y = ceil_div(op.h, kK7Rows);
-    const dim3 grid(planes * a.tiles_y);
-    ProfScope ps(FVP_K_CONV, s, 2.0 * op.cin * op.cout * 49.0 * op.h * op.w * planes, 1, prof_level() >= 2);
-#define FVP_K7(W_, NCG_)                                                                                      \
-  {                                                                                                            \
-    static LdsOptIn optin;                                                                                     \
-    auto k = &k_conv7<W_, NCG_>;                                                                               \
-    const size_t lds = std::max(kK7LdsPad, size_t(4 * NCG_) * conv7_cs(W_, kK7Rows) * sizeof(float));          \
-    if (int e = lds_opt_in(optin, reinterpret_cast<const void*>(k), lds)) return e;                            \
-    hipLaunchKernelGGL(k, grid, dim3(W_ / 16 * 64), lds, s, a);                                                \
-  }
-    if (ncg == 4) {
-      if (op.w == 64) FVP_K7(64, 4) else FVP_K7(128, 4)
-    } else {
-      if (op.w == 64) FVP_K7(64, 5) else FVP_K7(128, 5)
-    }
-#undef FVP_K7
-    return launch_status();
-  }
-  // Accumulator budget: CB*PB = 4 tiles of 32x32 per wave (~141 registers, 3 waves/SIMD).
-  // Large grids keep all couts in one workgroup (input tile staged once); small grids split
-  // couts over blockIdx.y and shrink the pixel tile so that more CUs get work.
-  // PAIR layout (cout <= 16): tile columns are pixel pairs
-  const bool pair = !tr && op.pair_off > 0 && !kNoPair && op.w % 4 == 0;
-  const int wq = pair ? op.w / 2 : op.w;           // tile columns per image row
-  const int hw = op.h * wq;
-  const long px_total = long(hw) * planes;
-  int CB = CBfull, PB = 4 / CBfull;
-  if (px_total / (128 * PB) < 512) {
-    CB = 1;
-    PB = 4;
-    while (PB > 1 && (px_total + 128 * PB - 1) / (128 * PB) * CBfull < 512) PB >>= 1;
-  }
-  if (kForcePB && CB * kForcePB <= 4) PB = kForcePB;
+      double(4 * (op.cin <= 16 ? 4 : 5)) * op.h * op.w * 4.0 < 2147483648.0)
+    return ConvForm::K7;
+  // PAIR layout (cout <= 16): tile columns are pixel pairs; instances exist for the 7x7 kernel only
+  if (paired) return kh == 7 && kw == 7 ? ConvForm::Pair7 : ConvForm::Refused;
   // split K over the four waves (k_conv_dma<..., KS>): 3x3 layers with >= 64 channels on maps of 256 .. 576 pixels
   // (CenterNet's 20x20 level: reductions of 576-1152 terms, 13-52 pixel blocks per plane).  Measured on the MI355X:
   // 128->128 @20x20 32.3 -> 18.7 us at one plane (33.3 -> 31.0 at eight); the 40x40 level gains nothing at one plane
   // (18.9 -> 18.2 us) and doubles at eight planes (every workgroup stages the same weight slice), so it stays on the
   // plain form.  A SHAPE rule (map size, channels), never the number of planes: a frame's result does not depend on
   // the batch it is computed in.
-  const bool ksplit = !tr && !pair && !kNoKSplit && kh == 3 && kw == 3 && op.w % 4 == 0 && op.w <= 32 && op.h * op.w >= 256 &&
-                      op.h * op.w <= 576 && op.cinp >= 64 && op.cinp % 8 == 0 && !kNoDma;
-  if (ksplit) {
-    CB = 1;
-    PB = 1;                                               // one image row (plus masked lanes) per workgroup
-  }
-  a.ablate = kAblate;
+  if (!kNoKSplit && kh == 3 && kw == 3 && op.w % 4 == 0 && op.w <= 32 && op.h * op.w >= 256 && op.h * op.w <= 576 &&
+      op.cinp >= 64 && op.cinp % 8 == 0 && !kNoDma)
+    return ConvForm::KSplit;
+  return ConvForm::Direct;
+}
+
+static double conv_flops(const FvpConvOp& op, int planes) {   // algorithmic FLOPs (2*MAC on the true channel counts)
+  const double taps = op.kind == FVP_OP_CONVT2 ? (op.h > 1 ? 4.0 : 2.0) : double(op.kh * op.kw);
+  return 2.0 * op.cin * op.cout * taps * op.h * op.w * planes;
+}
+
+static int launch_reg_form(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s) {
+  const bool tr = op.kind == FVP_OP_CONVT2;
+  const int hw = op.h * op.w;
+  const int NB = reg_blocks(op, tr), mode = reg_mode(tr, a.w2 != nullptr);
+  a.m_tpp = make_magic(hw / 32);
+  a.m_w = make_magic(op.w);
+  a.zeros = params;
+  const size_t lds = (size_t(op.cinp) * 32 * NB + 3 * size_t(op.coutp) + (mode == 2 ? 32 * 32 + 96 : 0)) * sizeof(float);
+  const int occ = kRegWgs ? kRegWgs : (op.cinp * NB <= 128 ? 3 : 2);
+  const int per_cu = std::max(1, std::min(occ, int((160 * 1024) / (lds + 256))));
+  const int nz = tr ? 2 : 1;
+  const long want = (long(planes) * (hw / 32) + 3) / 4;       // four 32-pixel tiles per workgroup
+  const int gx = int(std::min<long>(want, std::max(1, persistent_workgroups() * per_cu / nz)));
+  dim3 grid(gx, 1, nz);
+  ProfScope ps(FVP_K_CONV, s, conv_flops(op, planes), 1, prof_level() >= 2);
+#define FVP_X(K_, NB_, MODE_) if (op.cinp == K_ && NB == NB_ && mode == MODE_) return launch_reg<K_, NB_, MODE_>(a, grid, lds, s);
+  FVP_REG_INSTANCES(FVP_X)
+#undef FVP_X
+  return FVP_ELIMIT;                                   // (not reached: conv_form() answers Reg for the listed instances only)
+}
+
+// Tile (TN planes x TH rows x TW columns per workgroup), channel chunk CC, fdiv magics, LDS layout and grid of one
+// k_conv / k_conv_dma launch in the TPair, KSplit, Pair7 or Direct form, with CB x PB accumulator tiles (32 couts x 128
+// pixels, 32 pixels with split K) per wave; a.wrow and a.ntapT are set by the caller.  The paired transposed form is
+// the direct one with one tap, full-width tiles only and LDS-DMA staging whatever kNoDma says.
+static int plan_tiles(const FvpConvOp& op, const float* params, int planes, ConvForm form, int CB, int PB, ConvArgs& a, dim3* grid,
+                      size_t* lds_bytes) {
+  const bool tr = op.kind == FVP_OP_CONVT2;
+  const bool pair = form == ConvForm::Pair7, tpair = form == ConvForm::TPair, ksplit = form == ConvForm::KSplit;
+  const int kh = tr ? 1 : op.kh, kw = tr ? 1 : op.kw;   // (a transposed conv is one 1x1 conv per tap: blockIdx.z)
+  const int wq = pair ? op.w / 2 : op.w;             // tile columns per image row
+  const int hw = op.h * wq;
   const int TP = ksplit ? PB * 32 : PB * 128;
-  if (hw <= TP) {                       // whole planes per tile
-    a.TW = op.w;
-    a.TH = op.h;
-    a.TN = TP / hw > 0 ? TP / hw : 1;
-  } else if (wq <= TP) {                // full-width row bands
-    a.TW = op.w;
-    a.TH = TP / wq;
-    a.TN = 1;
-  } else {
-    a.TW = TP;
-    a.TH = 1;
-    a.TN = 1;
-  }
+  // whole planes per tile (hw <= TP), else full-width row bands (wq <= TP), else pieces of a row
+  a.TW = wq <= TP ? op.w : TP;
+  a.TH = hw <= TP ? op.h : wq <= TP ? TP / wq : 1;
+  a.TN = hw <= TP ? TP / hw : 1;
+  if (tpair && a.TW != op.w) return FVP_ELIMIT;
   a.m_w = make_magic(pair ? wq : a.TW);
   a.m_thw = make_magic(a.TH * (pair ? wq : a.TW));
   a.tiles_x = ceil_div(op.w, a.TW);
   a.tiles_y = ceil_div(op.h, a.TH);
-  const int pgroups = ceil_div(planes, a.TN);
-  // channel chunk: largest even CC that fits the LDS budget
   a.vec = (a.TW == op.w && op.w % 4 == 0) ? 1 : 0;
-  a.dma = (a.vec && !kNoDma) ? 1 : 0;
+  a.dma = (a.vec && (tpair || !kNoDma)) ? 1 : 0;
   a.zeros = params;
+  // channel chunk: largest even CC that fits the LDS budget
   const int twp = a.dma ? a.TW + 4 : (a.vec ? a.TW + 8 : a.TW + kw - 1);
-  const int kt = pair ? kw + 1 : kw;               // taps per kernel row in the packed layout
+  const int kt = pair ? kw + 1 : kw;             // taps per kernel row in the packed layout
   const size_t per_ch = (size_t(a.TN) * (a.TH + kh - 1) * twp + size_t(kh) * kt * 32 * CB) * sizeof(float);
   // the pipelined kernel keeps two chunks in LDS
-  const size_t epi_bytes = a.dma ? (size_t(3) * op.coutp + 96) * sizeof(float) : 0;   // BN vectors in LDS (k_conv_dma)
+  const size_t epi_bytes = a.dma ? (size_t(3) * op.coutp + 96) * sizeof(float) : 0;   // BN vectors (+ the fused 1x1 conv's) in LDS (k_conv_dma)
   int CC = int((kLdsBudget - 64 - epi_bytes) / (per_ch * (a.dma ? 2 : 1))) & ~1;
   if (CC > op.cinp) CC = op.cinp;
   if (CC < 2) return FVP_ELIMIT;
@@ -1271,15 +1154,16 @@ static int plan_and_launch(const FvpConvOp& op, const float* params, float* cons
     while (CC > 2 && size_t(CC) * a.TN * (a.TH + kh - 1) * (a.TW / 4 + 1) + 1 > 2048) CC -= 2;
   for (int d = CC; d >= 2 && d * 2 > CC; d -= 2)      // avoid a ragged last chunk when a close divisor exists
     if (op.cinp % d == 0) { CC = d; break; }
-  if (ksplit) {                                       // whole groups of four channel pairs; no ragged chunk
+  if (ksplit) {                                     // whole groups of four channel pairs; no ragged chunk
     if (!a.dma || CC < 8) return FVP_ELIMIT;
     CC &= ~7;
     while (CC > 8 && op.cinp % CC) CC -= 8;
   }
   a.CC = CC;
-  if (a.dma && !buf_dma_range_ok(a.TN, op.cin, op.h, op.w, double(op.cinp) * kh * kt * a.wrow)) return FVP_ELIMIT;
-  // stage_buf packs an item's channel-in-chunk into 8 bits
-  if (a.dma && CC > 255) return FVP_ELIMIT;
+  // Two refusals the paired transposed form has never had (its plan was a separate copy of this one); its outcomes are
+  // kept as they were: the byte-offset range of the chunk DMA, and stage_buf's 8 bits for an item's channel-in-chunk
+  if (a.dma && !tpair && !buf_dma_range_ok(a.TN, op.cin, op.h, op.w, double(op.cinp) * kh * kt * a.wrow)) return FVP_ELIMIT;
+  if (a.dma && !tpair && CC > 255) return FVP_ELIMIT;
   a.m_qpr = make_magic(a.dma ? a.TW / 4 + 1 : a.TW / 4);
   a.m_rpc = make_magic(a.TN * (a.TH + kh - 1));
   a.m_thp = make_magic(a.TH + kh - 1);
@@ -1292,26 +1176,159 @@ static int plan_and_launch(const FvpConvOp& op, const float* params, float* cons
     a.epi_off = int(lds / sizeof(float));
     lds += epi_bytes;
   }
-  dim3 grid(a.tiles_x * a.tiles_y * pgroups, CBfull / CB, a.ntapT);
-  // algorithmic FLOPs (2*MAC on the true channel counts)
-  const double taps = tr ? double(a.ntapT) : double(op.kh * op.kw);
-  ProfScope ps(FVP_K_CONV, s, 2.0 * op.cin * op.cout * taps * op.h * op.w * planes, 1, prof_level() >= 2);
+  *lds_bytes = lds;
+  *grid = dim3(a.tiles_x * a.tiles_y * ceil_div(planes, a.TN), tpair ? 1 : op.coutp / 32 / CB, a.ntapT);
+  return 0;
+}
+
+// ConvTranspose(k2,s2) in the paired form: CB = 2*coutp/32 accumulator blocks (both column taps), grid.z = output row parity.
+static int launch_tpair_form(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s) {
+  const int CB = 2 * op.coutp / 32, PB = 4 / CB;         // (2,2) or (4,1)
+  dim3 grid;
+  size_t lds;
+  if (int e = plan_tiles(op, params, planes, ConvForm::TPair, CB, PB, a, &grid, &lds)) return e;
+  ProfScope ps(FVP_K_CONV, s, conv_flops(op, planes), 1, prof_level() >= 2);
+  if (CB == 2)
+    hipLaunchKernelGGL((k_conv_dma<1, 1, 2, 2, false, true>), grid, dim3(256), lds, s, a);
+  else
+    hipLaunchKernelGGL((k_conv_dma<1, 1, 4, 1, false, true>), grid, dim3(256), lds, s, a);
+  return launch_status();
+}
+
+// 7x7 front conv on k_conv7: one workgroup per plane and band of kK7Rows rows
+static int launch_k7_form(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s) {
+  a.wts = params + op.pair_off + size_t(op.cinp) * 7 * 8 * 32;       // the k-grouped copy behind the pixel-pair copy
+  a.tiles_y = ceil_div(op.h, kK7Rows);
+  const dim3 grid(planes * a.tiles_y);
+  ProfScope ps(FVP_K_CONV, s, conv_flops(op, planes), 1, prof_level() >= 2);
+  if (op.cin <= 16) return op.w == 64 ? launch_k7<64, 4>(a, grid, s) : launch_k7<128, 4>(a, grid, s);
+  return op.w == 64 ? launch_k7<64, 5>(a, grid, s) : launch_k7<128, 5>(a, grid, s);
+}
+
+// The direct forms of k_conv / k_conv_dma.  Direct: all couts per workgroup (CB = coutp/32), the tile shaped to cover full
+// image rows where possible.  KSplit: one image row (plus masked lanes) per workgroup.  Pair7: tile columns are pixel pairs.
+static int launch_direct_form(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s, ConvForm form) {
+  const bool tr = op.kind == FVP_OP_CONVT2, pair = form == ConvForm::Pair7, ksplit = form == ConvForm::KSplit;
+  const int kh = tr ? 1 : op.kh, kw = tr ? 1 : op.kw;
+  // Accumulator budget: CB*PB = 4 tiles of 32x32 per wave (~141 registers, 3 waves/SIMD).  Large grids keep all couts in one
+  // workgroup (input tile staged once); small grids split couts over blockIdx.y and shrink the pixel tile so that more CUs get work.
+  const int CBfull = op.coutp / 32;
+  const long px_total = long(op.h * (pair ? op.w / 2 : op.w)) * planes;
+  int CB = CBfull, PB = 4 / CBfull;
+  if (px_total / (128 * PB) < 512) {
+    CB = 1;
+    PB = 4;
+    while (PB > 1 && (px_total + 128 * PB - 1) / (128 * PB) * CBfull < 512) PB >>= 1;
+  }
+  if (kForcePB && CB * kForcePB <= 4) PB = kForcePB;
+  if (ksplit) CB = PB = 1;
+  dim3 grid;
+  size_t lds;
+  if (int e = plan_tiles(op, params, planes, form, CB, PB, a, &grid, &lds)) return e;
+  ProfScope ps(FVP_K_CONV, s, conv_flops(op, planes), 1, prof_level() >= 2);
   if (ksplit) {
     hipLaunchKernelGGL((k_conv_dma<3, 3, 1, 1, false, false, true>), grid, dim3(256), lds, s, a);
     return launch_status();
   }
-  if (pair) {
-    if (!a.dma || CB != 1 || kh != 7 || kw != 7) return FVP_ELIMIT;
-    a.wts = params + op.pair_off;
-    switch (PB) {
-      case 1: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 1, true>), grid, dim3(256), lds, s, a); break;
-      case 2: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 2, true>), grid, dim3(256), lds, s, a); break;
-      case 4: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 4, true>), grid, dim3(256), lds, s, a); break;
-      default: return FVP_ELIMIT;
-    }
-    return launch_status();
+  if (!pair) return dispatch_conv(kh, kw, CB, PB, a, grid, lds, s);
+  if (!a.dma || CB != 1) return FVP_ELIMIT;
+  a.wts = params + op.pair_off;
+  switch (PB) {
+    case 1: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 1, true>), grid, dim3(256), lds, s, a); break;
+    case 2: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 2, true>), grid, dim3(256), lds, s, a); break;
+    case 4: hipLaunchKernelGGL((k_conv_dma<7, 7, 1, 4, true>), grid, dim3(256), lds, s, a); break;
+    default: return FVP_ELIMIT;
   }
-  return dispatch_conv(kh, kw, CB, PB, a, grid, lds, s);
+  return launch_status();
+}
+
+// the launch arguments that do not depend on the form
+static ConvArgs base_args(const FvpConvOp& op, const float* params, float* const* bufs, int planes, const uint8_t* plane_valid,
+                          int valid_div, float* pool_dst, const FvpConvOp* head) {
+  ConvArgs a{};
+  a.pool_dst = pool_dst;
+  if (head) {                                          // (eligibility: fused_head())
+    a.w2 = params + head->w_off;
+    a.epi2 = params + head->e_off;
+    a.dst2 = bufs[head->dst];
+    a.cout2 = head->cout;
+    a.flags2 = head->flags;
+  }
+  a.src = bufs[op.src];
+  a.dst = bufs[op.dst];
+  a.res = op.res >= 0 ? bufs[op.res] : nullptr;
+  a.wts = params + op.w_off;
+  a.epi = params + op.e_off;
+  a.plane_valid = plane_valid;
+  a.valid_div = valid_div > 0 ? valid_div : 1;
+  a.m_vd = make_magic(a.valid_div);
+  a.planes = planes;
+  a.cin = op.cin; a.cinp = op.cinp; a.cout = op.cout; a.coutp = op.coutp;
+  a.H = op.h; a.W = op.w;
+  a.flags = op.flags;
+  a.ablate = kAblate;
+  const bool tr = op.kind == FVP_OP_CONVT2;
+  a.osx = tr ? 2 : 1;
+  a.osy = tr && op.h > 1 ? 2 : 1;
+  a.ntapT = tr ? (op.h > 1 ? 4 : 2) : 1;
+  a.tapT_w = tr ? 2 : 1;
+  a.OH = op.h * a.osy; a.OW = op.w * a.osx;
+  a.wrow = op.coutp;
+  return a;
+}
+
+static int plan_and_launch(const FvpConvOp& op, const float* params, float* const* bufs, int planes, const uint8_t* plane_valid,
+                           int valid_div, hipStream_t s, float* pool_dst, const FvpConvOp* head) {
+  ConvArgs a = base_args(op, params, bufs, planes, plane_valid, valid_div, pool_dst, head);
+  if (double(planes) * std::max(op.cin, op.cout) * a.OH * a.OW >= 2147483648.0) return FVP_ELIMIT;
+  const ConvForm form = conv_form(op, planes, pool_dst != nullptr, head != nullptr);
+  if (op.kind == FVP_OP_CONVT2 && (form == ConvForm::Reg || form == ConvForm::TPair)) {
+    a.wts = params + op.pair_off;                      // the paired copy: both column taps in one weight row,
+    a.wrow = 2 * op.coutp;                             // grid.z = output row parity
+    a.ntapT = 2;
+    a.tapT_w = 1;
+  }
+  switch (form) {
+    case ConvForm::Reg: return launch_reg_form(op, a, params, planes, s);
+    case ConvForm::TPair: return launch_tpair_form(op, a, params, planes, s);
+    case ConvForm::Wino: return wino_plan_and_launch(op, a, params, planes, s);
+    case ConvForm::K7: return launch_k7_form(op, a, params, planes, s);
+    case ConvForm::Refused: return FVP_ELIMIT;
+    default: return launch_direct_form(op, a, params, planes, s, form);   // Direct, KSplit, Pair7
+  }
+}
+
+// A 2x2 max-pool that reads the output of a Winograd conv is produced by that conv's epilogue (one pooled value per
+// 2x2 output tile): the pool launch and its re-read of the map disappear.  Returns the index of that pool op, or -1.
+static int fused_pool(const FvpConvOp* ops, int nops, int i, int nbufs, int planes) {
+  const FvpConvOp& op = ops[i];
+  if (kNoPoolFuse || conv_form(op, planes, false, false) != ConvForm::Wino) return -1;
+  for (int j = i + 1; j < nops && j < 64; ++j)
+    if (ops[j].kind == FVP_OP_POOL2 && ops[j].src == op.dst && ops[j].h == op.h && ops[j].w == op.w && ops[j].h > 1 &&
+        ops[j].cin == op.cout && ops[j].dst >= 0 && ops[j].dst < nbufs)
+      return j;
+  return -1;
+}
+
+// A 32-cout paired transposed conv whose only consumer is the next op, a plain 1x1 conv (P2PNet's output layer): that
+// conv runs in the transposed conv's epilogue and the 32-channel map is never stored.  Returns that conv, or nullptr.
+static const FvpConvOp* fused_head(const FvpConvOp* ops, int nops, int i, int nbufs, int planes) {
+  const FvpConvOp& op = ops[i];
+  if (kNoHeadFuse || op.kind != FVP_OP_CONVT2 || op.coutp != 32 || i + 1 >= nops) return nullptr;
+  // the head's couts by form: k_conv_reg's MFMA head takes up to 32 output channels, k_conv_dma's fma-chain head stops at 16
+  const ConvForm form = conv_form(op, planes, false, true);
+  int max_cout = form == ConvForm::Reg ? 32 : form == ConvForm::TPair ? 16 : 0;
+  // Two outcomes kept from the rules this function replaces: no head on rows that are not whole quads, also where
+  // k_conv_reg takes the op; and the 17 .. 32-cout head is admitted without k_conv_reg's 2^31 limits (a map of > 3.7 M
+  // pixels: the paired transposed form then runs it).
+  if (form == ConvForm::TPair && reg_takes(op, planes, true, /*any_map_size=*/true)) max_cout = 32;
+  if (op.w % 4 != 0 || max_cout == 0) return nullptr;
+  const FvpConvOp& nx = ops[i + 1];
+  bool only = nx.kind == FVP_OP_CONV && nx.kh == 1 && nx.kw == 1 && nx.src == op.dst && nx.res < 0 && nx.cin == op.cout &&
+              nx.cinp == 32 && nx.coutp == 32 && nx.cout <= max_cout && nx.h == 2 * op.h && nx.w == 2 * op.w &&
+              nx.dst != op.dst && nx.dst >= 0 && nx.dst < nbufs;
+  for (int j = i + 2; j < nops && only; ++j) only = ops[j].src != op.dst && ops[j].res != op.dst;
+  return only ? &nx : nullptr;
 }
 
 }  // namespace fvp
@@ -1327,16 +1344,12 @@ extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* p
   double flops = 0.0;
   long nconv = 0;
   for (int i = 0; i < nops; ++i) {
-    const FvpConvOp& op = ops[i];
-    if (op.kind == FVP_OP_POOL2) continue;
-    const double taps = op.kind == FVP_OP_CONVT2 ? (op.h > 1 ? 4.0 : 2.0) : double(op.kh * op.kw);
-    flops += 2.0 * op.cin * op.cout * taps * op.h * op.w * planes;
+    if (ops[i].kind == FVP_OP_POOL2) continue;
+    flops += conv_flops(ops[i], planes);
     nconv += 1;
   }
   ProfScope stack_scope(FVP_K_CONV, as_stream(s), flops, nconv, prof_level() == 1);
-  // a 2x2 max-pool that reads the output of a Winograd conv is produced by that conv's epilogue
-  // (one pooled value per 2x2 output tile): the pool launch and its re-read of the map disappear
-  unsigned long long pooled = 0;                       // bit j: pool op j already done
+  unsigned long long pooled = 0;                       // bit j: pool op j already done (by a conv's epilogue)
   for (int i = 0; i < nops; ++i) {
     const FvpConvOp& op = ops[i];
     FVP_REQUIRE(op.src >= 0 && op.src < nbufs && op.dst >= 0 && op.dst < nbufs && op.res < nbufs);
@@ -1351,29 +1364,11 @@ extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* p
                          valid_div > 0 ? valid_div : 1, op.cin);
       rc = launch_status();
     } else if (op.kind == FVP_OP_CONV || op.kind == FVP_OP_CONVT2) {
-      float* pool_dst = nullptr;
-      if (op.kind == FVP_OP_CONV && op.wino_off > 0 && op.cin == op.cinp && op.cout % 32 == 0 && op.cout == op.coutp && !kNoWino && !kNoPoolFuse) {
-        for (int j = i + 1; j < nops && j < 64; ++j)
-          if (ops[j].kind == FVP_OP_POOL2 && ops[j].src == op.dst && ops[j].h == op.h && ops[j].w == op.w &&
-              ops[j].h > 1 && ops[j].cin == op.cout && ops[j].dst >= 0 && ops[j].dst < nbufs) {
-            pool_dst = bufs[ops[j].dst];
-            pooled |= 1ull << j;
-            break;
-          }
-      }
-      // a 32-cout paired transposed conv whose only consumer is the next op, a plain 1x1 conv (P2PNet's output
-      // layer): that conv runs in the transposed conv's epilogue and the 32-channel map is never stored
-      const FvpConvOp* head = nullptr;
-      if (op.kind == FVP_OP_CONVT2 && op.h > 1 && op.pair_off > 0 && !kNoPair && !kNoHeadFuse && op.w % 4 == 0 && op.coutp == 32 &&
-          i + 1 < nops) {
-        const FvpConvOp& nx = ops[i + 1];
-        bool only = nx.kind == FVP_OP_CONV && nx.kh == 1 && nx.kw == 1 && nx.src == op.dst && nx.res < 0 && nx.cin == op.cout &&
-                    nx.cinp == 32 && nx.coutp == 32 && (nx.cout <= 16 || reg_takes_fused_head(op, planes)) && nx.h == 2 * op.h && nx.w == 2 * op.w && nx.dst != op.dst &&
-                    nx.dst >= 0 && nx.dst < nbufs;
-        for (int j = i + 2; j < nops && only; ++j) only = ops[j].src != op.dst && ops[j].res != op.dst;
-        if (only) head = &nx;
-      }
-      rc = plan_and_launch(op, params, bufs, planes, plane_valid, valid_div, as_stream(s), pool_dst, head);
+      const int pool = fused_pool(ops, nops, i, nbufs, planes);
+      if (pool >= 0) pooled |= 1ull << pool;
+      const FvpConvOp* head = fused_head(ops, nops, i, nbufs, planes);
+      rc = plan_and_launch(op, params, bufs, planes, plane_valid, valid_div, as_stream(s),
+                           pool >= 0 ? bufs[ops[pool].dst] : nullptr, head);
       if (!rc && head) ++i;
     } else {
       rc = FVP_EINVAL;

@@ -107,10 +107,15 @@ inline size_t env_size(const char* name, size_t dflt) {
 // one persistent workgroup per CU (FVP_WINO_WGS overrides the count in the diagnostics build)
 int persistent_workgroups();
 
+// The kernel form that takes a conv op (fvp_conv.hip): k_conv_reg, paired transposed k_conv_dma, k_conv_wino, k_conv7,
+// split-K / pixel-pair / plain k_conv_dma (k_conv without LDS-DMA); Refused: no kernel has that shape (FVP_ELIMIT).
+enum class ConvForm { Reg, TPair, Wino, K7, KSplit, Pair7, Direct, Refused };
+ConvForm conv_form(const FvpConvOp& op, int planes, bool has_pool_dst, bool has_head);
+
 // ---- Winograd F(2x2,3x3) path (fvp_conv_wino.hip) ----
 // shapes the Winograd kernel takes (a SHAPE rule, never the number of planes)
 bool wino_shape_ok(int h, int w, int cinp, int coutp);
-// plans and launches one 3x3 conv; `a` carries src / dst / res / epi / plane_valid / shape / flags / pool_dst
+// plans and launches one 3x3 conv (ConvForm::Wino); `a` carries src / dst / res / epi / plane_valid / shape / flags / pool_dst
 int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s);
 // state_dict weight [cout][cin][3][3] -> Winograd-domain copy at params + op.wino_off
 int wino_pack(const float* weight, const FvpConvOp& op, float* params, hipStream_t s);

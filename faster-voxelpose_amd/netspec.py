@@ -69,7 +69,7 @@ WINO_GENERIC = False
 
 def winograd_shape(kh, kw, h, w, cinp, coutp, cin=None, cout=None):
     """3x3 layers the F(2x2,3x3) kernel covers (the same rule as wino_tiling() in
-    csrc/fvp_conv.hip): decided from the layer shape alone, never from the batch."""
+    csrc/fvp_conv_wino.hip): decided from the layer shape alone, never from the batch."""
     if (kh, kw) != (3, 3) or h < 2 or h % 2 or w < 8 or w % 4 or (coutp != 32 and coutp % 64) or cinp % 4:
         return False
     if cin is not None and cin != cinp:          # whole channel chunks only (no padded input channels)

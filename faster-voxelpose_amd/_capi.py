@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 12           # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 13           # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -63,6 +63,7 @@ SIGNATURES = {
     "fvp_project_columns": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _G, _P, _I, _P, _P],
     "fvp_joint_evidence": [_P, _P, _P, _P, _I, _I, _G, _P, _P, _P],
     "fvp_track_update": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "fvp_track_smooth": [_P] * 12 + [_I] * 5 + [_F] * 6 + [_I, _P],
     "fvp_zmax": [_P, _P, C.c_long, _I, _P],
     "fvp_person_boxes": [_P, _I, _P, _P, _P, _P, _P],
     "fvp_project_individual": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _G, _P, _P],

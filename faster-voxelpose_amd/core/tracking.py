@@ -4,8 +4,9 @@ ABI 12) and issues one launch per batch on the caller's current HIP stream.
 The forward returns ``fused_poses [B,N,J,5]`` ordered by NMS rank: the same person sits in slot 3 in one frame and in slot
 0 in the next.  ``update`` gives every valid slot a track id that follows the person through the frames of its camera
 sequence - nearest-pose greedy association with a distance gate, births, a maximum age and eviction from a full table, all
-defined bit for bit in include/fvp.h.  Not built: motion prediction, pose smoothing, re-identification after ``max_age``,
-Hungarian (optimal) assignment.
+defined bit for bit in include/fvp.h.  Pose smoothing and coasting through gaps consume the ids: core/smoothing.py
+(``PoseSmoother``).  Not built: motion prediction inside the association (it runs on the raw last pose, not on the smoother's
+predictions), re-identification after ``max_age``, Hungarian (optimal) assignment.
 
 No arithmetic happens here and nothing synchronises with the host: PyTorch is used for device memory and streams only.
 """

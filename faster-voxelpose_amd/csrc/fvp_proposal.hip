@@ -4,6 +4,8 @@
 // Tie rule (torch.topk leaves ties unspecified): value descending, then lowest flat index.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+
 #include "fvp_common.h"
 
 namespace fvp {
@@ -354,6 +356,163 @@ k_track_update(const float* __restrict__ poses, const int* __restrict__ frame_se
   for (int i = lane; i < T * J3; i += 64) trk_pose[size_t(s) * T * J3 + i] = s_trk[i];
 }
 
+// ---- track smoother (ABI 13): a One-Euro filter per joint of every track slot ----------------------------------------
+// The definition is in include/fvp.h.  Items (s, t, j) are independent over the whole batch: a thread owns one, keeps its
+// six state floats and the slot's id / age in registers and walks the B frames in order, skipping the frames of other
+// sequences - one launch per batch whatever B is, state read once at entry and written once at exit.  Every thread of a
+// slot recomputes the slot's id / age transition (integer, deterministic); the j == 0 thread writes it.  The state is
+// rewritten in place, so the J threads of a slot must all have read flt_id / flt_age before the j == 0 one stores them:
+// a workgroup is one wave and holds 64 / J WHOLE slots (J <= 32: at least two; 60 of 64 lanes at J = 15), the loads of a
+// wave precede its stores in program order, and no other wave touches the slot.  (The wave barrier behind the loads
+// emits no instruction; it is the hand-over point the CPU emulation needs, whose lanes do not run in lock-step.)  No
+// workgroup barrier, no LDS, no atomics.  Each element of smooth has one writer: the thread of the track slot a valid
+// detection sits in, or thread t == n for an invalid one (T >= N).  Latency-bound like k_track_update (B dependent
+// rounds of a few loads per thread): nothing is tuned.
+constexpr int kSmoothThreads = 64;
+static_assert(FVP_MAX_JOINTS <= kSmoothThreads, "a wave holds at least one whole slot");
+
+__device__ __forceinline__ float one_euro_alpha(float fc, float rate) {
+  const float r = __fdiv_rn(__fmul_rn(6.2831855f, fc), rate);
+  return __fdiv_rn(r, __fadd_rn(r, 1.0f));
+}
+
+__global__ void __launch_bounds__(kSmoothThreads)
+k_track_smooth(const float* __restrict__ poses, const int* __restrict__ frame_set, const int* __restrict__ ids,
+               const int* __restrict__ slots, const float* __restrict__ conf, float* __restrict__ flt_pose,
+               float* __restrict__ flt_vel, int* __restrict__ flt_id, int* __restrict__ flt_age,
+               float* __restrict__ smooth, float* __restrict__ track_poses, int* __restrict__ track_state, int B, int N,
+               int J, int nseq, int T, float rate, float min_cutoff, float beta, float d_cutoff, float conf_min,
+               float damp, int max_age) {
+  const int s = blockIdx.y, spb = kSmoothThreads / J, tl = int(threadIdx.x) / J;
+  const int t = blockIdx.x * spb + tl, j = int(threadIdx.x) - tl * J;
+  const bool active = tl < spb && t < T;
+  const size_t st = size_t(s) * T + t, sj = (st * J + j) * 3;
+  float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+  int id = -1, age = 0;
+  if (active) {
+    x0 = flt_pose[sj]; x1 = flt_pose[sj + 1]; x2 = flt_pose[sj + 2];
+    v0 = flt_vel[sj]; v1 = flt_vel[sj + 1]; v2 = flt_vel[sj + 2];
+    id = flt_id[st];
+    age = flt_age[st];
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (!active) return;
+  const float dt = __fdiv_rn(1.0f, rate), a_d = one_euro_alpha(d_cutoff, rate);
+
+#pragma unroll 1
+  for (int b = 0; b < B; ++b) {
+    const int fs = frame_set ? frame_set[b] : 0;
+    const size_t out = (size_t(b) * T + t) * J + j;            // this item's row of track_poses
+    if (fs != s) {
+      // a frame of no sequence: nobody owns it, the workgroups of sequence 0 write it as invalid
+      if (s == 0 && (fs < 0 || fs >= nseq)) {
+        if (track_poses) *reinterpret_cast<float4*>(track_poses + out * 4) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (track_state && j == 0) {
+          track_state[(size_t(b) * T + t) * 2] = -1;
+          track_state[(size_t(b) * T + t) * 2 + 1] = 0;
+        }
+        if (smooth && t < N) {
+          const size_t r = ((size_t(b) * N + t) * J + j) * 5;
+#pragma unroll
+          for (int c = 0; c < 5; ++c) smooth[r + c] = poses[r + c];
+        }
+      }
+      continue;
+    }
+    // the detections of this frame that sit in track slot t (a bit per n; the lowest one is measured), and whether
+    // detection slot n == t is an invalid one, which this thread copies through
+    unsigned mine = 0;
+    int first = -1;
+    bool copy = false;
+#pragma unroll 1
+    for (int n = 0; n < N; ++n) {
+      const int i = ids[size_t(b) * N + n], sl = slots[size_t(b) * N + n];
+      const bool ok = i >= 0 && sl >= 0 && sl < T;
+      if (ok && sl == t) {
+        mine |= 1u << n;
+        if (first < 0) first = n;
+      }
+      if (!ok && n == t) copy = true;
+    }
+    float flag = 0.0f;
+    if (first >= 0) {
+      const float* p = poses + ((size_t(b) * N + first) * J + j) * 5;
+      const float m0 = p[0], m1 = p[1], m2 = p[2];
+      const int nid = ids[size_t(b) * N + first];
+      age = 0;
+      if (id != nid) {                                         // a birth, a reuse or an eviction: the filter starts over
+        id = nid;
+        x0 = m0; x1 = m1; x2 = m2;
+        v0 = v1 = v2 = 0.0f;
+        flag = 1.0f;
+      } else {
+        const float e0 = __fsub_rn(m0, x0), e1 = __fsub_rn(m1, x1), e2 = __fsub_rn(m2, x2);
+        bool measured = fabsf(e0) <= FLT_MAX && fabsf(e1) <= FLT_MAX && fabsf(e2) <= FLT_MAX;      // false for NaN, Inf
+        if (measured && conf) measured = conf[(size_t(b) * N + first) * J + j] >= conf_min;
+        if (measured) {
+          v0 = __fadd_rn(v0, __fmul_rn(a_d, __fsub_rn(__fmul_rn(e0, rate), v0)));
+          v1 = __fadd_rn(v1, __fmul_rn(a_d, __fsub_rn(__fmul_rn(e1, rate), v1)));
+          v2 = __fadd_rn(v2, __fmul_rn(a_d, __fsub_rn(__fmul_rn(e2, rate), v2)));
+          const float sp = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(v0, v0), __fmul_rn(v1, v1)), __fmul_rn(v2, v2)));
+          const float a = one_euro_alpha(__fadd_rn(min_cutoff, __fmul_rn(beta, sp)), rate);
+          x0 = __fadd_rn(x0, __fmul_rn(a, e0));
+          x1 = __fadd_rn(x1, __fmul_rn(a, e1));
+          x2 = __fadd_rn(x2, __fmul_rn(a, e2));
+          flag = 1.0f;
+        } else {
+          v0 = __fmul_rn(v0, damp); v1 = __fmul_rn(v1, damp); v2 = __fmul_rn(v2, damp);
+          x0 = __fadd_rn(x0, __fmul_rn(v0, dt));
+          x1 = __fadd_rn(x1, __fmul_rn(v1, dt));
+          x2 = __fadd_rn(x2, __fmul_rn(v2, dt));
+        }
+      }
+    } else if (id >= 0) {
+      ++age;
+      if (age > max_age) {                                     // the slot is free
+        id = -1;
+        age = 0;
+      } else {                                                 // coasting: the predicted update
+        v0 = __fmul_rn(v0, damp); v1 = __fmul_rn(v1, damp); v2 = __fmul_rn(v2, damp);
+        x0 = __fadd_rn(x0, __fmul_rn(v0, dt));
+        x1 = __fadd_rn(x1, __fmul_rn(v1, dt));
+        x2 = __fadd_rn(x2, __fmul_rn(v2, dt));
+      }
+    }
+    if (smooth) {
+#pragma unroll 1
+      for (int n = first; n >= 0 && n < N; ++n) {
+        if (!(mine >> n & 1u)) continue;
+        const size_t r = ((size_t(b) * N + n) * J + j) * 5;
+        smooth[r] = x0;
+        smooth[r + 1] = x1;
+        smooth[r + 2] = x2;
+        smooth[r + 3] = poses[r + 3];
+        smooth[r + 4] = poses[r + 4];
+      }
+      if (copy) {
+        const size_t r = ((size_t(b) * N + t) * J + j) * 5;
+#pragma unroll
+        for (int c = 0; c < 5; ++c) smooth[r + c] = poses[r + c];
+      }
+    }
+    const bool live = id >= 0;
+    if (track_poses)
+      *reinterpret_cast<float4*>(track_poses + out * 4) =
+          live ? make_float4(x0, x1, x2, flag) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (track_state && j == 0) {
+      track_state[(size_t(b) * T + t) * 2] = id;
+      track_state[(size_t(b) * T + t) * 2 + 1] = age;
+    }
+  }
+
+  flt_pose[sj] = x0; flt_pose[sj + 1] = x1; flt_pose[sj + 2] = x2;
+  flt_vel[sj] = v0; flt_vel[sj + 1] = v1; flt_vel[sj + 2] = v2;
+  if (j == 0) {
+    flt_id[st] = id;
+    flt_age[st] = age;
+  }
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -421,5 +580,26 @@ extern "C" int fvp_track_update(const float* fused_poses, const int32_t* frame_s
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_track_update, dim3(nseq), dim3(64), 0, as_stream(s), fused_poses, frame_set, trk_pose, trk_id,
                      trk_age, next_id, ids, slots, costs, B, N, J, nseq, T, gate_mm, max_age);
+  return launch_status();
+}
+
+extern "C" int fvp_track_smooth(const float* fused_poses, const int32_t* frame_set, const int32_t* ids,
+                                const int32_t* slots, const float* joint_conf, float* flt_pose, float* flt_vel,
+                                int32_t* flt_id, int32_t* flt_age, float* smooth, float* track_poses,
+                                int32_t* track_state, int B, int N, int J, int nseq, int T, float rate_hz,
+                                float min_cutoff, float beta, float d_cutoff, float conf_min, float damp, int max_age,
+                                fvp_stream_t s) {
+  FVP_REQUIRE(fused_poses && ids && slots && flt_pose && flt_vel && flt_id && flt_age);
+  FVP_REQUIRE(smooth || track_poses || track_state);
+  FVP_REQUIRE(B >= 0 && N > 0 && J > 0 && nseq > 0 && T >= N && max_age >= 0);
+  // written so that a NaN fails every one of them
+  FVP_REQUIRE(rate_hz > 0.0f && min_cutoff > 0.0f && d_cutoff > 0.0f && beta >= 0.0f && damp >= 0.0f && damp <= 1.0f);
+  FVP_LIMIT(N <= kTrackDets && T <= kTrackSlots && J <= FVP_MAX_JOINTS);
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_track_smooth, dim3(ceil_div(T, kSmoothThreads / J), nseq), dim3(kSmoothThreads), 0, as_stream(s),
+                     fused_poses, frame_set, ids, slots, joint_conf, flt_pose, flt_vel, flt_id, flt_age, smooth,
+                     track_poses, track_state, B, N, J, nseq, T, rate_hz, min_cutoff, beta, d_cutoff, conf_min, damp,
+                     max_age);
   return launch_status();
 }

@@ -10,6 +10,9 @@ joint_conf [B,N,J])`` - every fused joint reprojected into every camera image wi
 per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``).  ``model.tracker = PoseTracker(cfg)``
 (core/tracking.py) makes ``forward`` also leave ``model.last_tracks = (ids [B,N], slots [B,N], costs [B,N])`` - one
 identity per person across the frames of a camera sequence, one more launch, no host synchronisation.
+``model.smoother = PoseSmoother(model.tracker)`` (core/smoothing.py) makes it also leave ``model.last_smooth = (smooth
+[B,N,J,5], track_poses [B,T,J,4], track_state [B,T,2])`` - the One-Euro-filtered pose of every track, slot-stable, unsupported
+joints and dropped-out tracks bridged by prediction; one more launch behind the tracker's.
 """
 import time
 
@@ -46,6 +49,11 @@ class FasterVoxelPoseNet(nn.Module):
         # same either way.  None: the forward issues exactly the launches it issues without the feature.
         self.tracker = None
         self.last_tracks = None
+        # a core.smoothing.PoseSmoother (needs `tracker`): forward() also calls smoother.update() behind the tracker's, on
+        # `last_tracks` - with `last_evidence[1]` as joint_conf when `evidence` is on - and keeps (smooth, track_poses,
+        # track_state) in `last_smooth`; the returned tuple is the same either way.  None: no launch more than without it.
+        self.smoother = None
+        self.last_smooth = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -67,6 +75,8 @@ class FasterVoxelPoseNet(nn.Module):
         if self.training:
             raise NotImplementedError("only the inference branch of FasterVoxelPoseNet.forward is implemented "
                                       "(call model.eval()); training losses are outside the hot path")
+        if self.smoother is not None and self.tracker is None:
+            raise capi.FvpError("model.smoother filters the tracks of model.tracker: set model.tracker (a PoseTracker) too")
         if views is not None:
             nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]
             frames = not nv12 and views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
@@ -132,6 +142,13 @@ class FasterVoxelPoseNet(nn.Module):
                                     f"built for nseq = {self.tracker.nseq}")
             fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
             self.last_tracks = self.tracker.update(fused_poses, sequences=fs)
+            if self.smoother is not None:
+                if self.smoother.nseq < self.tracker.nseq:
+                    raise capi.FvpError(f"model.smoother was built for nseq = {self.smoother.nseq}, model.tracker for "
+                                        f"{self.tracker.nseq}")
+                conf = self.last_evidence[1] if self.evidence else None
+                self.last_smooth = self.smoother.update(fused_poses, self.last_tracks[0], self.last_tracks[1],
+                                                        joint_conf=conf, sequences=fs)
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -148,7 +165,9 @@ class GraphedForward:
 
     With ``model.tracker`` set the tracker's launch is part of the graph and ``model.last_tracks`` holds static tensors;
     the track state lives in device memory, so it carries from replay to replay.  The warm-up and capture runs of the
-    constructor are forwards like any other and advance that state: call ``model.tracker.reset()`` after construction."""
+    constructor are forwards like any other and advance that state: call ``model.tracker.reset()`` after construction.
+    The same holds for ``model.smoother``: its launch is captured behind the tracker's, ``model.last_smooth`` holds static
+    tensors, the filter state carries across replays - call ``model.smoother.reset()`` after construction as well."""
 
     def __init__(self, model, meta, input_heatmaps, cameras, resize_transform, warmup=2):
         self.model = model
@@ -189,7 +208,9 @@ class PipelinedForward:
     Batches run on several streams and replicas, and a tracker needs the frames in time order on one stream: the
     pipeline takes no ``model.tracker`` (the constructor refuses a model that has one).  Keep the ``PoseTracker`` beside
     the pipeline and call ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after
-    ``event.wait()``."""
+    ``event.wait()``.  A ``model.smoother`` is refused for the same reason; the consumer-stream recipe is
+    ``ids, slots, _ = tracker.update(outputs[0], meta)`` followed by ``smoother.update(outputs[0], ids, slots, meta=meta)``
+    (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated)."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -205,6 +226,10 @@ class PipelinedForward:
         if model.tracker is not None:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.tracker = None "
                                 "and call tracker.update(outputs[0], meta) on the consumer stream in submit order")
+        if model.smoother is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.smoother = None "
+                                "and call smoother.update(outputs[0], ids, slots, meta=meta) behind tracker.update on the "
+                                "consumer stream in submit order")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):
@@ -267,7 +292,7 @@ class GraphedPipeline:
     Shapes, cameras and the sequence list are fixed at capture time (the reference's caller loop, function.py:136-148,
     feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, a tracker
     stays outside: ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after ``event.wait()``
-    (before the slot comes round again)."""
+    (before the slot comes round again), and ``smoother.update(outputs[0], ids, slots, meta=meta)`` behind it."""
 
     def __init__(self, model, depth, meta, input_heatmaps, cameras, resize_transform, streams=None, warmup=2):
         self.pipe = PipelinedForward(model, depth=depth, streams=streams)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 12
+#define FVP_ABI_VERSION 13
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -119,8 +119,9 @@ int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* f
 /* ---- pose tracker (ABI 12): one identity per person across the frames of a camera sequence -----------------------
  * No reference counterpart: the reference returns a bag of poses per frame, ordered by NMS rank.  This call gives every
  * valid slot of fused_poses [B][N][J][5] a track id that follows the person from frame to frame, on the device, in one
- * launch per batch and without host synchronisation.  Nearest-pose greedy association only: no motion prediction, no
- * pose smoothing, no re-identification after max_age, no optimal (Hungarian) assignment.
+ * launch per batch and without host synchronisation.  Nearest-pose greedy association only: no motion prediction (the
+ * poses are smoothed, and tracks coast through gaps, by fvp_track_smooth below, which consumes ids / slots; association
+ * itself runs on the raw last pose), no re-identification after max_age, no optimal (Hungarian) assignment.
  * State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
  *   trk_pose [nseq][T][J][3] fp32, trk_id [nseq][T] int32 (-1 = free slot), trk_age [nseq][T] int32, next_id [nseq] int32;
  *   the initial state is all ids -1, all ages 0, next_id 0 (the poses of free slots are never read).
@@ -148,6 +149,54 @@ int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* f
 int fvp_track_update(const float* fused_poses, const int32_t* frame_set, float* trk_pose, int32_t* trk_id,
                      int32_t* trk_age, int32_t* next_id, int32_t* ids /* [B,N] */, int32_t* slots /* [B,N] */,
                      float* costs /* [B,N] */, int B, int N, int J, int nseq, int T, float gate_mm, int max_age,
+                     fvp_stream_t s);
+
+/* ---- track smoother (ABI 13): steady, slot-stable poses per track ---------------------------------------------------
+ * fvp_track_smooth is a One-Euro filter (Casiez et al. 2012) per joint, in fp32.  Every operation is rounded on its own;
+ * sums and products are evaluated exactly as written below; `/` and sqrtf are the correctly rounded forms.
+ * State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
+ *   flt_pose [nseq][T][J][3] fp32, flt_vel [nseq][T][J][3] fp32 (mm/s), flt_id [nseq][T] int32 (-1 = free; initially all
+ *   -1), flt_age [nseq][T] int32 (initially 0).
+ * Inputs per call: fused_poses [B][N][J][5]; frame_set [B] (NULL = sequence 0); ids [B][N] and slots [B][N] as
+ * fvp_track_update wrote them for the same batch; joint_conf [B][N][J] (fvp_joint_evidence) or NULL.
+ * Parameters: rate_hz, min_cutoff, beta, d_cutoff, conf_min, damp (floats), max_age (int).
+ * Constants, computed in the kernel: dt = 1.0f / rate_hz;  alpha(fc) = r / (r + 1.0f) with r = (6.2831855f * fc) / rate_hz;
+ * a_d = alpha(d_cutoff).
+ * Frames are consumed in batch order, sequences are independent.  A frame whose frame_set entry is outside [0, nseq)
+ * changes no state, and its outputs are written as invalid.  For frame b of sequence s, every track slot t:
+ *   1. n = the lowest detection slot with ids[b][n] >= 0 and slots[b][n] == t, if any (a slot with ids >= 0 whose slots
+ *      entry is outside [0, T) is treated like one with ids < 0 everywhere below);
+ *   2. n exists and flt_id[s][t] != ids[b][n] - a birth, a reuse, an eviction: the slot is (re)initialised.  For every j:
+ *      x^ = fused_poses[b][n][j][0:3], v^ = 0, flag = 1;  flt_id = ids[b][n], flt_age = 0;
+ *   3. n exists and the id is the same: flt_age = 0 and every joint j on its own, with x = fused_poses[b][n][j][0:3]:
+ *        e_c = x_c - x^_c for c = 0,1,2;
+ *        the joint is MEASURED when (joint_conf is NULL or joint_conf[b][n][j] >= conf_min) and fabsf(e_c) <= FLT_MAX
+ *        for all three c (a NaN or Inf never counts as measured):
+ *          v_c = e_c * rate_hz;  v^_c = v^_c + a_d * (v_c - v^_c);
+ *          sp = sqrtf((v^_0*v^_0 + v^_1*v^_1) + v^_2*v^_2);  a = alpha(min_cutoff + beta * sp);
+ *          x^_c = x^_c + a * e_c;  flag = 1;
+ *        otherwise it is PREDICTED:  v^_c = v^_c * damp;  x^_c = x^_c + v^_c * dt;  flag = 0;
+ *   4. no n and flt_id[s][t] >= 0: flt_age += 1; if it is now > max_age, flt_id = -1, flt_age = 0 and the slot is free
+ *      (its x^, v^ stay as they are and are never read); otherwise every joint takes the PREDICTED update of 3 (coasting);
+ *   5. outputs - each may be NULL, not all of them; every element of a non-NULL output is written by every call:
+ *        smooth [B][N][J][5]: for a valid slot, columns 0:3 are the x^ of its track slot after this frame and columns 3:5
+ *          are copied from fused_poses; an invalid slot (ids < 0) is copied from fused_poses unchanged (the layout
+ *          core/metrics.py, utils/vis.py and fvp_joint_evidence take);
+ *        track_poses [B][T][J][4]: (x^_0, x^_1, x^_2, flag) after this frame - person-stable: a person keeps its row t
+ *          for the life of the track, coasting frames included; a free slot is four zeros;
+ *        track_state [B][T][2] int32: (flt_id, flt_age) after this frame; a free slot is (-1, 0).
+ * Consequence (tested): with the tracker's own max_age, flt_id == trk_id after every call, and flt_age == trk_age in every
+ * live slot (the tracker leaves max_age + 1 in a slot it has freed; here a freed slot's age is 0).
+ * The tracker still associates against the raw last pose: predictions are not fed back into association.
+ * One thread per (s, t, j) walks the batch; one launch per batch.  FVP_EINVAL: a null required pointer (frame_set and
+ * joint_conf excepted; all three outputs null), N, J or nseq < 1, T < N, max_age < 0, rate_hz, min_cutoff or d_cutoff not
+ * > 0, beta not >= 0, damp outside [0, 1] (a NaN fails every one of these comparisons);  FVP_ELIMIT as for
+ * fvp_track_update.  Nothing is written when an error is returned.  B == 0 returns 0 without a launch. */
+int fvp_track_smooth(const float* fused_poses, const int32_t* frame_set, const int32_t* ids, const int32_t* slots,
+                     const float* joint_conf, float* flt_pose, float* flt_vel, int32_t* flt_id, int32_t* flt_age,
+                     float* smooth /* [B,N,J,5] */, float* track_poses /* [B,T,J,4] */,
+                     int32_t* track_state /* [B,T,2] */, int B, int N, int J, int nseq, int T, float rate_hz,
+                     float min_cutoff, float beta, float d_cutoff, float conf_min, float damp, int max_age,
                      fvp_stream_t s);
 
 /* z-max of already materialised cubes [n][Z] -> [n] (n = B*J*X*Y): the first statement of

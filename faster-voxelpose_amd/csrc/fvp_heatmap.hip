@@ -226,6 +226,159 @@ k_ingest_nv12(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, i
   });
 }
 
+// ---- poses back onto the camera frames (fvp_draw_poses, include/fvp.h) ---------------------------------------------------
+// Third image kernel of this file, the only one that WRITES frames.  Tile-centric: a workgroup owns 64 x 16 pixels of one
+// frame (a wave's lanes are 64 consecutive x of one row: 192 contiguous bytes), walks the frame's N * (J + L) primitives in
+// chunks of the block size - a thread builds one primitive in Q4 from `views` and appends it to a list in LDS when its
+// bounding box meets the tile - and every pixel thread runs the list and ORs 1 << n into a coverage mask per pixel (hence
+// N <= 32).  A pixel with a non-zero mask loads its three bytes, blends the persons in ascending bit order and stores them;
+// a tile whose lists stay empty never touches the frame.  A wave per limb writing its own pixels would race wherever two
+// people overlap, and the blend order would depend on scheduling.
+// All coverage arithmetic is exact integer arithmetic (a disc is the capsule with a == b).
+struct DrawPrm {
+  uint8_t limb[64][2];
+  uint8_t pal[64][3];
+};
+constexpr int kDrawTW = 64, kDrawTH = 16, kDrawThreads = 256;
+constexpr int kDrawRows = kDrawTH / (kDrawThreads / kDrawTW);                        // pixels (rows) per thread
+constexpr int kDrawMaxN = 32, kDrawMaxL = 64, kDrawMaxP = 64, kDrawMaxR = 1024;
+constexpr int kDrawMaxChunks = (kDrawMaxN * (FVP_MAX_JOINTS + kDrawMaxL) + kDrawThreads - 1) / kDrawThreads;
+
+// Q4 position of joint `vj` (index into views / 4) when it is drawable.  |.| <= 32768 fails for NaN and Inf.
+__device__ __forceinline__ bool draw_joint(const float* __restrict__ views, const float* __restrict__ conf, float conf_min,
+                                           long vj, long cj, int& qx, int& qy) {
+  const float px = views[4 * vj], py = views[4 * vj + 1], depth = views[4 * vj + 2];
+  bool ok = depth > 0.0f && fabsf(px) <= 32768.0f && fabsf(py) <= 32768.0f;
+  if (conf) ok = ok && conf[cj] >= conf_min;
+  qx = ok ? int(rintf(px * 16.0f)) : 0;                   // exact product, round-half-even
+  qy = ok ? int(rintf(py * 16.0f)) : 0;
+  return ok;
+}
+
+// Pixel centre p against the capsule of half-width rad around a-b (include/fvp.h).  Coordinates are below 2^20 in
+// magnitude, so t, dd and the cross product stay below 2^42 and rad^2 * dd below 2^62: everything but the square of the
+// cross product fits 64 bits.  That square is a 128-bit product (c_hi 2^32 + c_lo)^2; whenever c_hi != 0 it is >= 2^64 and
+// exceeds the right-hand side, otherwise it is c_lo * c_lo, which fits - so only the low product is ever formed.
+__device__ __forceinline__ bool draw_covers(int px, int py, int ax, int ay, int bx, int by, int rad) {
+  const long long dx = bx - ax, dy = by - ay, wx = px - ax, wy = py - ay;
+  const long long r2 = (long long)rad * rad;
+  const long long t = wx * dx + wy * dy, dd = dx * dx + dy * dy;
+  if (t <= 0) return wx * wx + wy * wy <= r2;
+  if (t >= dd) {
+    const long long ex = px - bx, ey = py - by;
+    return ex * ex + ey * ey <= r2;
+  }
+  const long long c = wx * dy - wy * dx;
+  const unsigned long long a = (unsigned long long)(c < 0 ? -c : c);
+  return (a >> 32) == 0 && a * a <= (unsigned long long)r2 * (unsigned long long)dd;
+}
+
+// the CPU emulation's read fences (tests/hipemu) see the frame bytes a pixel thread is about to load: the test of "pixels
+// that nothing covers are not read"; nothing on the device
+__device__ __forceinline__ void draw_note_read(const uint8_t* p) {
+#if defined(HIPEMU)
+  if (hipemu::nfences) hipemu::fenced_read_check(p);
+#else
+  (void)p;
+#endif
+}
+
+__global__ void __launch_bounds__(kDrawThreads)
+k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* __restrict__ views,
+             const int32_t* __restrict__ ids, const float* __restrict__ conf, int N, int J, int L, int P, DrawPrm prm,
+             int R, int W, int alpha, float conf_min) {
+  // cnt[c]: hits of chunk c (never reset: no barrier between a chunk's readers and the next chunk's writers); the lists
+  // alternate, chunk c + 2 rewrites list c & 1 only after the barrier of chunk c + 1, which every reader of c has passed
+  __shared__ int cnt[kDrawMaxChunks];
+  __shared__ int seg[2][kDrawThreads][4];
+  __shared__ int tag[2][kDrawThreads];                 // person | radius << 8
+  __shared__ unsigned pcol[kDrawMaxN];                 // r | g << 8 | b << 16 | drawn << 24
+  const int tid = threadIdx.x;
+  const int f = blockIdx.z, b = f / V;                 // frame b * V + v
+  const int x0 = blockIdx.x * kDrawTW, y0 = blockIdx.y * kDrawTH;
+  const int x1 = (x0 + kDrawTW < Ws ? x0 + kDrawTW : Ws) - 1, y1 = (y0 + kDrawTH < Hs ? y0 + kDrawTH : Hs) - 1;
+  if (tid < kDrawMaxChunks) cnt[tid] = 0;
+  if (tid < N) {
+    const int key = ids ? ids[long(b) * N + tid] : tid;
+    unsigned col = 0;
+    if (key >= 0) {
+      const uint8_t* c = prm.pal[key % P];
+      col = unsigned(c[0]) | (unsigned(c[1]) << 8) | (unsigned(c[2]) << 16) | (1u << 24);
+    }
+    pcol[tid] = col;
+  }
+  __syncthreads();
+  const int x = x0 + (tid & (kDrawTW - 1)), yb = y0 + tid / kDrawTW;      // this thread's pixels: rows yb + 4 r
+  unsigned mask[kDrawRows];
+#pragma unroll
+  for (int r = 0; r < kDrawRows; ++r) mask[r] = 0u;
+  const int per = J + L, NP = N * per;
+  for (int base = 0, c = 0; base < NP; base += kDrawThreads, ++c) {
+    const int i = base + tid;
+    if (i < NP) {
+      const int n = i / per, r = i - n * per;
+      if (pcol[n] >> 24) {
+        int j0 = r, j1 = r, rad = R;
+        if (r >= J) {
+          j0 = prm.limb[r - J][0];
+          j1 = prm.limb[r - J][1];
+          rad = W;
+        }
+        const long vrow = (long(f) * N + n) * J, crow = (long(b) * N + n) * J;
+        int ax, ay, bx, by;
+        bool ok = draw_joint(views, conf, conf_min, vrow + j0, crow + j0, ax, ay);
+        bx = ax;
+        by = ay;
+        if (j1 != j0) {
+          const bool ok1 = draw_joint(views, conf, conf_min, vrow + j1, crow + j1, bx, by);
+          ok = ok && ok1;
+        }
+        const int lox = (ax < bx ? ax : bx) - rad, hix = (ax < bx ? bx : ax) + rad;
+        const int loy = (ay < by ? ay : by) - rad, hiy = (ay < by ? by : ay) + rad;
+        if (ok && hix >= 16 * x0 && lox <= 16 * x1 && hiy >= 16 * y0 && loy <= 16 * y1) {
+          const int k = atomicAdd(&cnt[c], 1);
+          int* e = seg[c & 1][k];
+          e[0] = ax;
+          e[1] = ay;
+          e[2] = bx;
+          e[3] = by;
+          tag[c & 1][k] = n | (rad << 8);
+        }
+      }
+    }
+    __syncthreads();
+    const int m = cnt[c];
+    for (int k = 0; k < m; ++k) {
+      const int* e = seg[c & 1][k];
+      const int ax = e[0], ay = e[1], bx = e[2], by = e[3], tg = tag[c & 1][k];
+      const unsigned bit = 1u << (tg & 31);
+#pragma unroll
+      for (int r = 0; r < kDrawRows; ++r)
+        if (draw_covers(16 * x, 16 * (yb + r * (kDrawThreads / kDrawTW)), ax, ay, bx, by, tg >> 8)) mask[r] |= bit;
+    }
+  }
+  if (x >= Ws) return;
+  const int na = 256 - alpha;
+#pragma unroll
+  for (int r = 0; r < kDrawRows; ++r) {
+    const int y = yb + r * (kDrawThreads / kDrawTW);
+    if (mask[r] == 0u || y >= Hs) continue;
+    uint8_t* p = frames + ((size_t(f) * Hs + y) * Ws + x) * 3;
+    draw_note_read(p);
+    int c0 = p[0], c1 = p[1], c2 = p[2];
+    for (int n = 0; n < N; ++n)
+      if ((mask[r] >> n) & 1u) {
+        const unsigned col = pcol[n];
+        c0 = (int(col & 255u) * alpha + c0 * na + 128) >> 8;
+        c1 = (int((col >> 8) & 255u) * alpha + c1 * na + 128) >> 8;
+        c2 = (int((col >> 16) & 255u) * alpha + c2 * na + 128) >> 8;
+      }
+    p[0] = uint8_t(c0);
+    p[1] = uint8_t(c1);
+    p[2] = uint8_t(c2);
+  }
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -304,5 +457,29 @@ extern "C" int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int H
   FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
   hipLaunchKernelGGL(k_ingest_nv12, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), y, uv, N, Hs, Ws, q,
                      p, H, W, nhwc8, nchw);
+  return launch_status();
+}
+
+extern "C" int fvp_draw_poses(uint8_t* frames, int B, int V, int Hs, int Ws, const float* views, const int32_t* ids,
+                              const float* joint_conf, int N, int J, const int32_t* limbs, int L, const uint8_t* palette,
+                              int P, int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s) {
+  FVP_REQUIRE(frames && views && palette && (limbs || L <= 0));
+  FVP_REQUIRE(B >= 0 && V >= 0 && N >= 1 && J >= 1 && Hs >= 1 && Ws >= 1 && P >= 1 && L >= 0);
+  FVP_REQUIRE(alpha >= 1 && alpha <= 256 && joint_radius_q4 >= 0 && joint_radius_q4 <= kDrawMaxR && limb_half_q4 >= 0 &&
+              limb_half_q4 <= kDrawMaxR && !std::isnan(conf_min));
+  FVP_LIMIT(N <= kDrawMaxN && J <= FVP_MAX_JOINTS && V <= FVP_MAX_VIEWS && L <= kDrawMaxL && P <= kDrawMaxP);
+  FVP_LIMIT(Hs <= 16384 && Ws <= 16384 && long(B) * V <= 65535);
+  DrawPrm prm = {};
+  for (int l = 0; l < L; ++l)
+    for (int e = 0; e < 2; ++e) {
+      FVP_REQUIRE(limbs[2 * l + e] >= 0 && limbs[2 * l + e] < J);
+      prm.limb[l][e] = uint8_t(limbs[2 * l + e]);
+    }
+  for (int i = 0; i < 3 * P; ++i) prm.pal[i / 3][i % 3] = palette[i];
+  if (long(B) * V == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_draw_poses, dim3(ceil_div(Ws, kDrawTW), ceil_div(Hs, kDrawTH), unsigned(B * V)), dim3(kDrawThreads),
+                     0, as_stream(s), frames, V, Hs, Ws, views, ids, joint_conf, N, J, L, P, prm, joint_radius_q4,
+                     limb_half_q4, alpha, conf_min);
   return launch_status();
 }

@@ -13,6 +13,8 @@ identity per person across the frames of a camera sequence, one more launch, no 
 ``model.smoother = PoseSmoother(model.tracker)`` (core/smoothing.py) makes it also leave ``model.last_smooth = (smooth
 [B,N,J,5], track_poses [B,T,J,4], track_state [B,T,2])`` - the One-Euro-filtered pose of every track, slot-stable, unsupported
 joints and dropped-out tracks bridged by prediction; one more launch behind the tracker's.
+``model.overlay = PoseOverlay(cfg)`` (utils/overlay.py; needs ``evidence`` and ``uint8`` camera frames as ``views``) makes it
+also draw the skeletons into the caller's frames, in place, coloured by track id when a tracker is set.
 """
 import time
 
@@ -54,6 +56,13 @@ class FasterVoxelPoseNet(nn.Module):
         # track_state) in `last_smooth`; the returned tuple is the same either way.  None: no launch more than without it.
         self.smoother = None
         self.last_smooth = None
+        # a utils.overlay.PoseOverlay (needs `evidence` and uint8 camera frames as `views`): forward() also draws the
+        # skeletons into the caller's frames, in place, behind the tracker and the smoother - from `last_evidence[0]`, or,
+        # with a smoother, from one more joint_evidence() of `last_smooth[0]` kept in `last_overlay_views` - with
+        # `last_tracks[0]` as colour keys and `last_evidence[1]` as joint_conf; the returned tuple is the same either way.
+        # None: no launch more than without it.
+        self.overlay = None
+        self.last_overlay_views = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -77,6 +86,14 @@ class FasterVoxelPoseNet(nn.Module):
                                       "(call model.eval()); training losses are outside the hot path")
         if self.smoother is not None and self.tracker is None:
             raise capi.FvpError("model.smoother filters the tracks of model.tracker: set model.tracker (a PoseTracker) too")
+        canvas = None
+        if self.overlay is not None:
+            if not self.evidence:
+                raise capi.FvpError("model.overlay draws the pixels of model.last_evidence: set model.evidence = True too")
+            if not torch.is_tensor(views) or views.dtype != torch.uint8:
+                raise capi.FvpError("model.overlay draws into the camera frames: pass them as views, uint8 [B,V,Hs,Ws,3] "
+                                    "(NV12 surfaces, float images and input_heatmaps alone leave nothing to draw on)")
+            canvas = views
         if views is not None:
             nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]
             frames = not nv12 and views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
@@ -149,6 +166,16 @@ class FasterVoxelPoseNet(nn.Module):
                 conf = self.last_evidence[1] if self.evidence else None
                 self.last_smooth = self.smoother.update(fused_poses, self.last_tracks[0], self.last_tracks[1],
                                                         joint_conf=conf, sequences=fs)
+        if canvas is not None:
+            # ingest has read the frames on this stream already.  With a smoother the picture shows the steady poses:
+            # their pixels are one more evidence launch on the staging copy of this forward
+            px, self.last_overlay_views = self.last_evidence[0], None
+            if self.smoother is not None:
+                px = self.engine.joint_evidence(self.last_smooth[0], input_heatmaps, meta, cameras, resize_transform,
+                                                reuse_staging=True)[0]
+                self.last_overlay_views = px
+            self.overlay.draw(canvas, px, ids=self.last_tracks[0] if self.tracker is not None else None,
+                              joint_conf=self.last_evidence[1])
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -210,7 +237,9 @@ class PipelinedForward:
     the pipeline and call ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after
     ``event.wait()``.  A ``model.smoother`` is refused for the same reason; the consumer-stream recipe is
     ``ids, slots, _ = tracker.update(outputs[0], meta)`` followed by ``smoother.update(outputs[0], ids, slots, meta=meta)``
-    (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated)."""
+    (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated).  A ``model.overlay`` is
+    refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
+    ``model.joint_evidence``."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -230,6 +259,9 @@ class PipelinedForward:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.smoother = None "
                                 "and call smoother.update(outputs[0], ids, slots, meta=meta) behind tracker.update on the "
                                 "consumer stream in submit order")
+        if model.overlay is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.overlay = None "
+                                "and call overlay.draw(frames, views, ids) on the consumer stream")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):
@@ -292,7 +324,8 @@ class GraphedPipeline:
     Shapes, cameras and the sequence list are fixed at capture time (the reference's caller loop, function.py:136-148,
     feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, a tracker
     stays outside: ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after ``event.wait()``
-    (before the slot comes round again), and ``smoother.update(outputs[0], ids, slots, meta=meta)`` behind it."""
+    (before the slot comes round again), and ``smoother.update(outputs[0], ids, slots, meta=meta)`` behind it; an overlay
+    likewise (``overlay.draw(frames, views, ids)`` on the consumer stream)."""
 
     def __init__(self, model, depth, meta, input_heatmaps, cameras, resize_transform, streams=None, warmup=2):
         self.pipe = PipelinedForward(model, depth=depth, streams=streams)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 13
+#define FVP_ABI_VERSION 14
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -444,6 +444,43 @@ int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int Hs, int Ws, 
                     long y_frame_stride, long uv_frame_stride, /* bytes */
                     int standard, const float inv[6], const float mean[3], const float stdv[3], int H, int W,
                     uint16_t* nhwc8, float* nchw, fvp_stream_t s);
+
+/* ---- skeleton overlay (ABI 14): the poses drawn onto the camera frames they were computed from ------------------------
+ * Counterpart of the reference's host-side lib/utils/vis.py::save_image_with_poses (cv2.circle / cv2.line per view), on the
+ * device and in place.  frames [B*V][Hs][Ws][3] uint8 is the contiguous HWC layout of fvp_ingest_frames: frame b*V + v
+ * belongs to views[b][v].  views [B][V][N][J][4] = (px, py, depth, s) as fvp_joint_evidence writes them (pixels of the
+ * ORIGINAL frame); ids [B][N] int32 (fvp_track_update) or NULL; joint_conf [B][N][J] or NULL.  limbs [L][2] int32 (joint
+ * index pairs) and palette [P][3] uint8 are HOST memory and go to the kernel by value, as inv / mean do.
+ * Geometry: integers, in sixteenths of a pixel ("Q4"); the centre of pixel (x, y) is (16x, 16y).
+ * Drawable joint (b,v,n,j): depth > 0, and |px| <= 32768 and |py| <= 32768 (fp32 compares: a NaN or an Inf fails them),
+ *   and joint_conf is NULL or joint_conf[b][n][j] >= conf_min (a NaN confidence is not drawable).  Its Q4 position is
+ *   q = (rint(px * 16), rint(py * 16)), round-half-even; the product by 16 is exact.
+ * Drawn person: n of frame b is drawn iff ids is NULL or ids[b][n] >= 0; its colour is palette[key % P] with
+ *   key = ids ? ids[b][n] : n.  Invalid slots need no flag: fvp_joint_evidence writes them as zeros, so their depth is 0.
+ * Primitives of person n in view v: a disc of radius joint_radius_q4 around every drawable joint; for every limb (i, k)
+ *   whose two joints are both drawable, the capsule of half-width limb_half_q4 around the segment a = q_i, b = q_k.
+ * Coverage of a pixel centre p, all comparisons in exact integers:
+ *   disc:     |p-q|^2 <= R^2;
+ *   capsule:  with d = b-a, w = p-a, t = w.d, dd = d.d:   t <= 0 (this includes dd == 0): |w|^2 <= W^2;
+ *             t >= dd: |p-b|^2 <= W^2;   otherwise: (w_x d_y - w_y d_x)^2 <= W^2 * dd.
+ * Paint: for every pixel of the frame, for n = 0 .. N-1 in ascending order: if any primitive of person n covers the pixel,
+ *   then ONCE per person and per channel   dst = (colour * alpha + dst * (256 - alpha) + 128) >> 8.
+ *   Overlapping primitives of one person blend once; persons blend one over the other in slot order.  Pixels that nothing
+ *   covers are neither read nor written.
+ * One workgroup per 64 x 16 pixel tile of one frame collects the primitives whose bounding box meets the tile and its
+ * pixels evaluate them: no two workgroups write the same byte, the result does not depend on scheduling.
+ * FVP_EINVAL: null frames, views or palette; limbs null with L > 0; B or V < 0; N, J, Hs, Ws or P < 1; L < 0; a limb index
+ * outside [0, J); alpha outside [1, 256]; joint_radius_q4 or limb_half_q4 outside [0, 1024]; NaN conf_min.
+ * FVP_ELIMIT: N > 32, J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS, L > 64, P > 64, Hs or Ws > 16384, B * V > 65535 (one grid
+ * plane per frame).  Nothing is written when an error is returned.  B * V == 0 returns 0 without a launch.
+ * No bit-compatibility with OpenCV's rasteriser is claimed.  Not built: NV12 output, text labels, anti-aliasing, pitched
+ * frames. */
+int fvp_draw_poses(uint8_t* frames /* [B*V][Hs][Ws][3], in place */, int B, int V, int Hs, int Ws,
+                   const float* views /* [B][V][N][J][4] of fvp_joint_evidence */,
+                   const int32_t* ids /* [B][N] or NULL */, const float* joint_conf /* [B][N][J] or NULL */,
+                   int N, int J, const int32_t* limbs /* HOST [L][2], may be NULL when L == 0 */, int L,
+                   const uint8_t* palette /* HOST [P][3] */, int P,
+                   int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

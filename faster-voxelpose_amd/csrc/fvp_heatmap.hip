@@ -283,21 +283,20 @@ __device__ __forceinline__ void draw_note_read(const uint8_t* p) {
 #endif
 }
 
-__global__ void __launch_bounds__(kDrawThreads)
-k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* __restrict__ views,
-             const int32_t* __restrict__ ids, const float* __restrict__ conf, int N, int J, int L, int P, DrawPrm prm,
-             int R, int W, int alpha, float conf_min) {
-  // cnt[c]: hits of chunk c (never reset: no barrier between a chunk's readers and the next chunk's writers); the lists
-  // alternate, chunk c + 2 rewrites list c & 1 only after the barrier of chunk c + 1, which every reader of c has passed
-  __shared__ int cnt[kDrawMaxChunks];
-  __shared__ int seg[2][kDrawThreads][4];
-  __shared__ int tag[2][kDrawThreads];                 // person | radius << 8
-  __shared__ unsigned pcol[kDrawMaxN];                 // r | g << 8 | b << 16 | drawn << 24
-  const int tid = threadIdx.x;
-  const int f = blockIdx.z, b = f / V;                 // frame b * V + v
-  const int x0 = blockIdx.x * kDrawTW, y0 = blockIdx.y * kDrawTH;
-  const int x1 = (x0 + kDrawTW < Ws ? x0 + kDrawTW : Ws) - 1, y1 = (y0 + kDrawTH < Hs ? y0 + kDrawTH : Hs) - 1;
-  if (tid < kDrawMaxChunks) cnt[tid] = 0;
+// LDS of a draw kernel.  cnt[c]: hits of chunk c (never reset: no barrier between a chunk's readers and the next chunk's
+// writers); the lists alternate, chunk c + 2 rewrites list c & 1 only after the barrier of chunk c + 1, which every reader of
+// c has passed
+struct DrawLds {
+  int cnt[kDrawMaxChunks];
+  int seg[2][kDrawThreads][4];
+  int tag[2][kDrawThreads];                            // person | radius << 8
+  unsigned pcol[kDrawMaxN];                            // three colour bytes | drawn << 24
+};
+
+// Before the first barrier: empty lists, and thread n looks up person n's colour (prm.pal is in the surface's own channels)
+__device__ __forceinline__ void draw_begin(DrawLds& s, int tid, const int32_t* __restrict__ ids, int b, int N, int P,
+                                           const DrawPrm& prm) {
+  if (tid < kDrawMaxChunks) s.cnt[tid] = 0;
   if (tid < N) {
     const int key = ids ? ids[long(b) * N + tid] : tid;
     unsigned col = 0;
@@ -305,57 +304,87 @@ k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* _
       const uint8_t* c = prm.pal[key % P];
       col = unsigned(c[0]) | (unsigned(c[1]) << 8) | (unsigned(c[2]) << 16) | (1u << 24);
     }
-    pcol[tid] = col;
+    s.pcol[tid] = col;
   }
+}
+
+// Primitive i of frame f (person i / (J + L); its joints first, then its limbs) built in Q4 and appended to list c & 1 when
+// its bounding box meets the tile [x0, x1] x [y0, y1]
+__device__ __forceinline__ void draw_collect(DrawLds& s, int c, int i, int f, int b, const float* __restrict__ views,
+                                             const float* __restrict__ conf, float conf_min, int N, int J, int L,
+                                             const DrawPrm& prm, int R, int W, int x0, int y0, int x1, int y1) {
+  const int per = J + L;
+  if (i >= N * per) return;
+  const int n = i / per, r = i - n * per;
+  if (!(s.pcol[n] >> 24)) return;
+  int j0 = r, j1 = r, rad = R;
+  if (r >= J) {
+    j0 = prm.limb[r - J][0];
+    j1 = prm.limb[r - J][1];
+    rad = W;
+  }
+  const long vrow = (long(f) * N + n) * J, crow = (long(b) * N + n) * J;
+  int ax, ay, bx, by;
+  bool ok = draw_joint(views, conf, conf_min, vrow + j0, crow + j0, ax, ay);
+  bx = ax;
+  by = ay;
+  if (j1 != j0) {
+    const bool ok1 = draw_joint(views, conf, conf_min, vrow + j1, crow + j1, bx, by);
+    ok = ok && ok1;
+  }
+  const int lox = (ax < bx ? ax : bx) - rad, hix = (ax < bx ? bx : ax) + rad;
+  const int loy = (ay < by ? ay : by) - rad, hiy = (ay < by ? by : ay) + rad;
+  if (ok && hix >= 16 * x0 && lox <= 16 * x1 && hiy >= 16 * y0 && loy <= 16 * y1) {
+    const int k = atomicAdd(&s.cnt[c], 1);
+    int* e = s.seg[c & 1][k];
+    e[0] = ax;
+    e[1] = ay;
+    e[2] = bx;
+    e[3] = by;
+    s.tag[c & 1][k] = n | (rad << 8);
+  }
+}
+
+// The thread's K pixel centres (Q4) against list c & 1, behind the barrier that follows draw_collect: bit n of mask[e] is set
+// when a primitive of person n covers pixel e
+template <int K>
+__device__ __forceinline__ void draw_scan(const DrawLds& s, int c, const int (&px)[K], const int (&py)[K], unsigned (&mask)[K]) {
+  const int m = s.cnt[c];
+  for (int k = 0; k < m; ++k) {
+    const int* e = s.seg[c & 1][k];
+    const int ax = e[0], ay = e[1], bx = e[2], by = e[3], tg = s.tag[c & 1][k];
+    const unsigned bit = 1u << (tg & 31);
+#pragma unroll
+    for (int r = 0; r < K; ++r)
+      if (draw_covers(px[r], py[r], ax, ay, bx, by, tg >> 8)) mask[r] |= bit;
+  }
+}
+
+__global__ void __launch_bounds__(kDrawThreads)
+k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* __restrict__ views,
+             const int32_t* __restrict__ ids, const float* __restrict__ conf, int N, int J, int L, int P, DrawPrm prm,
+             int R, int W, int alpha, float conf_min) {
+  __shared__ DrawLds s;
+  const int tid = threadIdx.x;
+  const int f = blockIdx.z, b = f / V;                 // frame b * V + v
+  const int x0 = blockIdx.x * kDrawTW, y0 = blockIdx.y * kDrawTH;
+  const int x1 = (x0 + kDrawTW < Ws ? x0 + kDrawTW : Ws) - 1, y1 = (y0 + kDrawTH < Hs ? y0 + kDrawTH : Hs) - 1;
+  draw_begin(s, tid, ids, b, N, P, prm);
   __syncthreads();
   const int x = x0 + (tid & (kDrawTW - 1)), yb = y0 + tid / kDrawTW;      // this thread's pixels: rows yb + 4 r
   unsigned mask[kDrawRows];
+  int px[kDrawRows], py[kDrawRows];
 #pragma unroll
-  for (int r = 0; r < kDrawRows; ++r) mask[r] = 0u;
-  const int per = J + L, NP = N * per;
+  for (int r = 0; r < kDrawRows; ++r) {
+    mask[r] = 0u;
+    px[r] = 16 * x;
+    py[r] = 16 * (yb + r * (kDrawThreads / kDrawTW));
+  }
+  const int NP = N * (J + L);
   for (int base = 0, c = 0; base < NP; base += kDrawThreads, ++c) {
-    const int i = base + tid;
-    if (i < NP) {
-      const int n = i / per, r = i - n * per;
-      if (pcol[n] >> 24) {
-        int j0 = r, j1 = r, rad = R;
-        if (r >= J) {
-          j0 = prm.limb[r - J][0];
-          j1 = prm.limb[r - J][1];
-          rad = W;
-        }
-        const long vrow = (long(f) * N + n) * J, crow = (long(b) * N + n) * J;
-        int ax, ay, bx, by;
-        bool ok = draw_joint(views, conf, conf_min, vrow + j0, crow + j0, ax, ay);
-        bx = ax;
-        by = ay;
-        if (j1 != j0) {
-          const bool ok1 = draw_joint(views, conf, conf_min, vrow + j1, crow + j1, bx, by);
-          ok = ok && ok1;
-        }
-        const int lox = (ax < bx ? ax : bx) - rad, hix = (ax < bx ? bx : ax) + rad;
-        const int loy = (ay < by ? ay : by) - rad, hiy = (ay < by ? by : ay) + rad;
-        if (ok && hix >= 16 * x0 && lox <= 16 * x1 && hiy >= 16 * y0 && loy <= 16 * y1) {
-          const int k = atomicAdd(&cnt[c], 1);
-          int* e = seg[c & 1][k];
-          e[0] = ax;
-          e[1] = ay;
-          e[2] = bx;
-          e[3] = by;
-          tag[c & 1][k] = n | (rad << 8);
-        }
-      }
-    }
+    draw_collect(s, c, base + tid, f, b, views, conf, conf_min, N, J, L, prm, R, W, x0, y0, x1, y1);
     __syncthreads();
-    const int m = cnt[c];
-    for (int k = 0; k < m; ++k) {
-      const int* e = seg[c & 1][k];
-      const int ax = e[0], ay = e[1], bx = e[2], by = e[3], tg = tag[c & 1][k];
-      const unsigned bit = 1u << (tg & 31);
-#pragma unroll
-      for (int r = 0; r < kDrawRows; ++r)
-        if (draw_covers(16 * x, 16 * (yb + r * (kDrawThreads / kDrawTW)), ax, ay, bx, by, tg >> 8)) mask[r] |= bit;
-    }
+    draw_scan(s, c, px, py, mask);
   }
   if (x >= Ws) return;
   const int na = 256 - alpha;
@@ -368,7 +397,7 @@ k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* _
     int c0 = p[0], c1 = p[1], c2 = p[2];
     for (int n = 0; n < N; ++n)
       if ((mask[r] >> n) & 1u) {
-        const unsigned col = pcol[n];
+        const unsigned col = s.pcol[n];
         c0 = (int(col & 255u) * alpha + c0 * na + 128) >> 8;
         c1 = (int((col >> 8) & 255u) * alpha + c1 * na + 128) >> 8;
         c2 = (int((col >> 16) & 255u) * alpha + c2 * na + 128) >> 8;
@@ -377,6 +406,81 @@ k_draw_poses(uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* _
     p[1] = uint8_t(c1);
     p[2] = uint8_t(c2);
   }
+}
+
+// The same overlay on an NV12 surface (fvp_draw_poses_nv12, include/fvp.h): the tile, the lists and the coverage test are
+// those of k_draw_poses; a thread owns one 2 x 2 luma quad and the (U, V) pair that serves it, so the chroma's box-filtered
+// coverage k_n needs no other lane.  A tile is 32 x 8 quads: a wave holds two quad rows - 64 contiguous luma bytes on each of
+// four rows, 64 contiguous chroma bytes on each of two.  Luma goes byte by byte (only covered bytes are touched), a chroma
+// pair as one 2-byte load and one 2-byte store.  Tiles start at even coordinates and Hs, Ws are even: a quad is inside the
+// frame or outside it as a whole, and no two workgroups touch the same byte.  prm.pal holds (Yc, Uc, Vc).
+struct DrawNv12Prm {
+  long y_pitch, uv_pitch, y_frame, uv_frame;
+};
+
+__global__ void __launch_bounds__(kDrawThreads)
+k_draw_poses_nv12(uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, DrawNv12Prm q, int V, int Hs, int Ws,
+                  const float* __restrict__ views, const int32_t* __restrict__ ids, const float* __restrict__ conf, int N,
+                  int J, int L, int P, DrawPrm prm, int R, int W, int alpha, float conf_min) {
+  __shared__ DrawLds s;
+  const int tid = threadIdx.x;
+  const int f = blockIdx.z, b = f / V;                 // frame b * V + v
+  const int x0 = blockIdx.x * kDrawTW, y0 = blockIdx.y * kDrawTH;
+  const int x1 = (x0 + kDrawTW < Ws ? x0 + kDrawTW : Ws) - 1, y1 = (y0 + kDrawTH < Hs ? y0 + kDrawTH : Hs) - 1;
+  draw_begin(s, tid, ids, b, N, P, prm);
+  __syncthreads();
+  const int x = x0 + 2 * (tid & (kDrawTW / 2 - 1)), y = y0 + 2 * (tid / (kDrawTW / 2));      // the quad's top-left pixel
+  unsigned mask[4];                                    // pixel e of the quad: (x + (e & 1), y + (e >> 1))
+  int px[4], py[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    mask[e] = 0u;
+    px[e] = 16 * (x + (e & 1));
+    py[e] = 16 * (y + (e >> 1));
+  }
+  const int NP = N * (J + L);
+  for (int base = 0, c = 0; base < NP; base += kDrawThreads, ++c) {
+    draw_collect(s, c, base + tid, f, b, views, conf, conf_min, N, J, L, prm, R, W, x0, y0, x1, y1);
+    __syncthreads();
+    draw_scan(s, c, px, py, mask);
+  }
+  const unsigned any = mask[0] | mask[1] | mask[2] | mask[3];
+  if (x >= Ws || y >= Hs || any == 0u) return;
+  uint8_t* pl = yp + long(f) * q.y_frame + long(y) * q.y_pitch + x;
+  uint16_t* pc = reinterpret_cast<uint16_t*>(uvp + long(f) * q.uv_frame + long(y >> 1) * q.uv_pitch + x);
+  int lum[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    lum[e] = 0;
+    if (mask[e]) {
+      const uint8_t* p = pl + (e >> 1) * q.y_pitch + (e & 1);
+      draw_note_read(p);
+      lum[e] = *p;
+    }
+  }
+  draw_note_read(reinterpret_cast<const uint8_t*>(pc));
+  const unsigned w = *pc;
+  int u = int(w & 255u), v = int(w >> 8);
+  const int na = 256 - alpha;
+  for (int n = 0; n < N; ++n)
+    if ((any >> n) & 1u) {
+      const unsigned col = s.pcol[n];
+      const int yc = int(col & 255u) * alpha + 128;
+      int k = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((mask[e] >> n) & 1u) {
+          lum[e] = (yc + lum[e] * na) >> 8;
+          ++k;
+        }
+      const int a = alpha * k;                         // 1 .. 1024: the share of the quad person n covers
+      u = (int((col >> 8) & 255u) * a + u * (1024 - a) + 512) >> 10;
+      v = (int((col >> 16) & 255u) * a + v * (1024 - a) + 512) >> 10;
+    }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (mask[e]) pl[(e >> 1) * q.y_pitch + (e & 1)] = uint8_t(lum[e]);
+  *pc = uint16_t(unsigned(u) | (unsigned(v) << 8));
 }
 
 }  // namespace fvp
@@ -460,26 +564,71 @@ extern "C" int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int H
   return launch_status();
 }
 
-extern "C" int fvp_draw_poses(uint8_t* frames, int B, int V, int Hs, int Ws, const float* views, const int32_t* ids,
-                              const float* joint_conf, int N, int J, const int32_t* limbs, int L, const uint8_t* palette,
-                              int P, int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s) {
-  FVP_REQUIRE(frames && views && palette && (limbs || L <= 0));
+// argument checks both draw exports share; limbs go into prm
+static int draw_args(int B, int V, int Hs, int Ws, const float* views, int N, int J, const int32_t* limbs, int L,
+                     const uint8_t* palette, int P, int joint_radius_q4, int limb_half_q4, int alpha, float conf_min,
+                     DrawPrm& prm) {
+  FVP_REQUIRE(views && palette && (limbs || L <= 0));
   FVP_REQUIRE(B >= 0 && V >= 0 && N >= 1 && J >= 1 && Hs >= 1 && Ws >= 1 && P >= 1 && L >= 0);
   FVP_REQUIRE(alpha >= 1 && alpha <= 256 && joint_radius_q4 >= 0 && joint_radius_q4 <= kDrawMaxR && limb_half_q4 >= 0 &&
               limb_half_q4 <= kDrawMaxR && !std::isnan(conf_min));
   FVP_LIMIT(N <= kDrawMaxN && J <= FVP_MAX_JOINTS && V <= FVP_MAX_VIEWS && L <= kDrawMaxL && P <= kDrawMaxP);
   FVP_LIMIT(Hs <= 16384 && Ws <= 16384 && long(B) * V <= 65535);
-  DrawPrm prm = {};
   for (int l = 0; l < L; ++l)
     for (int e = 0; e < 2; ++e) {
       FVP_REQUIRE(limbs[2 * l + e] >= 0 && limbs[2 * l + e] < J);
       prm.limb[l][e] = uint8_t(limbs[2 * l + e]);
     }
+  return 0;
+}
+
+extern "C" int fvp_draw_poses(uint8_t* frames, int B, int V, int Hs, int Ws, const float* views, const int32_t* ids,
+                              const float* joint_conf, int N, int J, const int32_t* limbs, int L, const uint8_t* palette,
+                              int P, int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s) {
+  FVP_REQUIRE(frames);
+  DrawPrm prm = {};
+  if (const int rc = draw_args(B, V, Hs, Ws, views, N, J, limbs, L, palette, P, joint_radius_q4, limb_half_q4, alpha,
+                               conf_min, prm))
+    return rc;
   for (int i = 0; i < 3 * P; ++i) prm.pal[i / 3][i % 3] = palette[i];
   if (long(B) * V == 0) return 0;
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_draw_poses, dim3(ceil_div(Ws, kDrawTW), ceil_div(Hs, kDrawTH), unsigned(B * V)), dim3(kDrawThreads),
                      0, as_stream(s), frames, V, Hs, Ws, views, ids, joint_conf, N, J, L, P, prm, joint_radius_q4,
                      limb_half_q4, alpha, conf_min);
+  return launch_status();
+}
+
+extern "C" int fvp_draw_poses_nv12(uint8_t* y, uint8_t* uv, int B, int V, int Hs, int Ws, long y_pitch, long uv_pitch,
+                                   long y_frame_stride, long uv_frame_stride, int standard, const float* views,
+                                   const int32_t* ids, const float* joint_conf, int N, int J, const int32_t* limbs, int L,
+                                   const uint8_t* palette, int P, int joint_radius_q4, int limb_half_q4, int alpha,
+                                   float conf_min, fvp_stream_t s) {
+  static const int coeffs[4][12] = {FVP_RGB2YUV_BT601_LIMITED_COEFFS, FVP_RGB2YUV_BT709_LIMITED_COEFFS,
+                                    FVP_RGB2YUV_BT601_FULL_COEFFS, FVP_RGB2YUV_BT709_FULL_COEFFS};
+  FVP_REQUIRE(y && uv);
+  DrawPrm prm = {};
+  if (const int rc = draw_args(B, V, Hs, Ws, views, N, J, limbs, L, palette, P, joint_radius_q4, limb_half_q4, alpha,
+                               conf_min, prm))
+    return rc;
+  FVP_REQUIRE(Hs % 2 == 0 && Ws % 2 == 0 && y_pitch >= Ws && uv_pitch >= Ws);
+  // a (U, V) pair is one 2-byte load and one 2-byte store
+  FVP_REQUIRE(uv_pitch % 2 == 0 && uv_frame_stride % 2 == 0 && reinterpret_cast<uintptr_t>(uv) % 2 == 0);
+  FVP_REQUIRE(standard >= 0 && standard < 4);
+  FVP_REQUIRE(long(B) * V <= 1 || (y_frame_stride >= (Hs - 1) * y_pitch + Ws && uv_frame_stride >= (Hs / 2 - 1) * uv_pitch + Ws));
+  const int* k = coeffs[standard];
+  for (int i = 0; i < P; ++i) {                        // palette entry -> (Yc, Uc, Vc), include/fvp.h; >> is arithmetic
+    const int r = palette[3 * i], g = palette[3 * i + 1], bl = palette[3 * i + 2];
+    for (int c = 0; c < 3; ++c) {
+      const int v = k[4 * c] + ((k[4 * c + 1] * r + k[4 * c + 2] * g + k[4 * c + 3] * bl + 32768) >> 16);
+      prm.pal[i][c] = uint8_t(v < 0 ? 0 : v > 255 ? 255 : v);
+    }
+  }
+  if (long(B) * V == 0) return 0;
+  const DrawNv12Prm q = {y_pitch, uv_pitch, y_frame_stride, uv_frame_stride};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_draw_poses_nv12, dim3(ceil_div(Ws, kDrawTW), ceil_div(Hs, kDrawTH), unsigned(B * V)),
+                     dim3(kDrawThreads), 0, as_stream(s), y, uv, q, V, Hs, Ws, views, ids, joint_conf, N, J, L, P, prm,
+                     joint_radius_q4, limb_half_q4, alpha, conf_min);
   return launch_status();
 }

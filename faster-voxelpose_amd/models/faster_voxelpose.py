@@ -14,7 +14,8 @@ identity per person across the frames of a camera sequence, one more launch, no 
 [B,N,J,5], track_poses [B,T,J,4], track_state [B,T,2])`` - the One-Euro-filtered pose of every track, slot-stable, unsupported
 joints and dropped-out tracks bridged by prediction; one more launch behind the tracker's.
 ``model.overlay = PoseOverlay(cfg)`` (utils/overlay.py; needs ``evidence`` and ``uint8`` camera frames as ``views``) makes it
-also draw the skeletons into the caller's frames, in place, coloured by track id when a tracker is set.
+also draw the skeletons into the caller's frames, in place, coloured by track id when a tracker is set; built with
+``nv12=True`` it also draws into ``Nv12Frames`` views, in the surface itself.
 """
 import time
 
@@ -56,7 +57,8 @@ class FasterVoxelPoseNet(nn.Module):
         # track_state) in `last_smooth`; the returned tuple is the same either way.  None: no launch more than without it.
         self.smoother = None
         self.last_smooth = None
-        # a utils.overlay.PoseOverlay (needs `evidence` and uint8 camera frames as `views`): forward() also draws the
+        # a utils.overlay.PoseOverlay (needs `evidence` and uint8 camera frames as `views`, or, built with nv12=True,
+        # Nv12Frames views, whose surface is then the canvas): forward() also draws the
         # skeletons into the caller's frames, in place, behind the tracker and the smoother - from `last_evidence[0]`, or,
         # with a smoother, from one more joint_evidence() of `last_smooth[0]` kept in `last_overlay_views` - with
         # `last_tracks[0]` as colour keys and `last_evidence[1]` as joint_conf; the returned tuple is the same either way.
@@ -90,9 +92,12 @@ class FasterVoxelPoseNet(nn.Module):
         if self.overlay is not None:
             if not self.evidence:
                 raise capi.FvpError("model.overlay draws the pixels of model.last_evidence: set model.evidence = True too")
-            if not torch.is_tensor(views) or views.dtype != torch.uint8:
+            # an NV12 surface is the decoder's own memory: drawn on only by an overlay built with nv12=True
+            if not (isinstance(views, Nv12Frames) and self.overlay.nv12) \
+                    and (not torch.is_tensor(views) or views.dtype != torch.uint8):
                 raise capi.FvpError("model.overlay draws into the camera frames: pass them as views, uint8 [B,V,Hs,Ws,3] "
-                                    "(NV12 surfaces, float images and input_heatmaps alone leave nothing to draw on)")
+                                    "(NV12 surfaces, float images and input_heatmaps alone leave nothing to draw on; "
+                                    "PoseOverlay(..., nv12=True) draws into Nv12Frames views, in the surface itself)")
             canvas = views
         if views is not None:
             nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]

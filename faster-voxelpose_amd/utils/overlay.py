@@ -1,16 +1,19 @@
 """Poses back onto the camera frames: ``PoseOverlay`` draws the skeletons of ``fvp_joint_evidence``'s ``views`` into the
 ``uint8`` frames they were computed from, on the device and in place (``fvp_draw_poses``, include/fvp.h, ABI 14) - the
 device-side counterpart of ``utils/vis.py::save_image_with_poses``, which copies frames and poses to the host and draws
-with matplotlib.  One launch on the caller's current HIP stream; no arithmetic on tensors happens here and nothing
-synchronises with the host: PyTorch is used for device memory and streams only.
+with matplotlib.  A decoder's NV12 surface (``dataset.images.Nv12Frames``) is drawn on directly, luma and chroma, with its
+own pitches and frame strides (``fvp_draw_poses_nv12``, ABI 15).  One launch on the caller's current HIP stream; no
+arithmetic on tensors happens here and nothing synchronises with the host: PyTorch is used for device memory and streams
+only.
 
-Not built: NV12 output, text labels, anti-aliasing, pitched frames.
+Not built: text labels, anti-aliasing, pitched RGB frames.
 """
 import ctypes as C
 
 import torch
 
 from .. import _capi as capi
+from ..dataset.images import Nv12Frames
 
 # person colours, RGB, indexed by track id (or by slot without ids) modulo the length
 PALETTE = [(230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
@@ -25,7 +28,7 @@ def _ptr(t):
 
 class PoseOverlay:
     """``PoseOverlay(num_joints_or_cfg, limbs=None, palette=None, joint_radius=8.0, limb_width=4.0, alpha=1.0,
-    conf_min=0.0)``
+    conf_min=0.0, nv12=False)``
 
     ``num_joints_or_cfg``  J, or a config (``DATASET.NUM_JOINTS``);
     ``limbs``              joint index pairs [L,2]; default: the table of ``utils.vis`` for J in {14, 15, 17};
@@ -34,10 +37,14 @@ class PoseOverlay:
     ``limb_width``         width of a limb, pixels (cv2.line of thickness 4 there);
     ``alpha``              opacity in (0, 1]: 1 paints, lower values blend with the frame;
     ``conf_min``           with ``joint_conf`` given, a joint below it - and every limb ending in it - is left out.
+    ``nv12``               True: ``model.overlay`` may draw into ``Nv12Frames`` views.  In place means into the
+                           decoder's own surface, which the decoder may still hold as a reference picture: the flag is
+                           the caller's statement that the surface is theirs to paint.  ``draw()``
+                           itself takes an ``Nv12Frames`` either way.
     Radius and half width are rounded to sixteenths of a pixel, ``alpha`` to 1/256."""
 
     def __init__(self, num_joints_or_cfg, limbs=None, palette=None, joint_radius=8.0, limb_width=4.0, alpha=1.0,
-                 conf_min=0.0, _lib=None):
+                 conf_min=0.0, nv12=False, _lib=None):
         # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
         self._injected = _lib is not None
         self.lib = _lib if _lib is not None else capi.load()
@@ -58,6 +65,7 @@ class PoseOverlay:
                                                             for c in self.palette):
             raise capi.FvpError(f"palette: 1 to {MAX_COLOURS} RGB triples of bytes")
         self.conf_min = float(conf_min)
+        self.nv12 = bool(nv12)
         if self.conf_min != self.conf_min or not (joint_radius >= 0 and limb_width >= 0 and 0 < alpha <= 1):
             raise capi.FvpError(f"PoseOverlay needs joint_radius, limb_width >= 0, alpha in (0, 1] and a conf_min that is "
                                 f"not NaN (joint_radius = {joint_radius}, limb_width = {limb_width}, alpha = {alpha}, "
@@ -76,15 +84,23 @@ class PoseOverlay:
         """Draw ``views [B,V,N,J,4]`` (``last_evidence[0]``, or ``joint_evidence(...)[0]`` of any poses) into ``frames``
         ``uint8 [B,V,Hs,Ws,3]`` in place and return ``frames``.  ``ids [B,N]`` int32 (``last_tracks[0]``): the colour
         follows the track and slots with a negative id are left out; None: the colour follows the slot.  ``joint_conf
-        [B,N,J]`` (``last_evidence[1]``): joints below ``conf_min`` are left out.  One launch on the current stream."""
+        [B,N,J]`` (``last_evidence[1]``): joints below ``conf_min`` are left out.  One launch on the current stream.
+        ``frames`` may also be an ``Nv12Frames`` with leading dimensions ``[B,V]``: both planes are drawn on in place,
+        with the surface's pitches, frame strides and colour standard (the palette stays RGB)."""
         f, v = frames, views
-        if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3 or not f.is_contiguous():
+        nv12 = isinstance(f, Nv12Frames)
+        if nv12:
+            if len(f.lead) != 2:
+                raise capi.FvpError(f"an NV12 surface to draw on must have leading dimensions [B,V], got {f.lead}")
+            B, V, Hs, Ws = f.lead[0], f.lead[1], f.Hs, f.Ws
+        elif not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3 or not f.is_contiguous():
             raise capi.FvpError("frames must be a contiguous uint8 tensor [B,V,Hs,Ws,3] (HWC camera frames), got "
                                 f"{getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))}")
         if not self._injected and f.device.type != "cuda":
             raise capi.FvpError(f"frames live on {f.device}: the overlay runs on a ROCm GPU device (spelled 'cuda:N' in "
                                 "PyTorch-ROCm); there is no CPU fallback")
-        B, V, Hs, Ws = f.shape[:4]
+        if not nv12:
+            B, V, Hs, Ws = f.shape[:4]
         if not torch.is_tensor(v) or v.dtype != torch.float32 or v.device != f.device or v.dim() != 5 \
                 or tuple(v.shape[:2]) != (B, V) or tuple(v.shape[3:]) != (self.J, 4) or not v.is_contiguous():
             raise capi.FvpError(f"views must be a contiguous float32 tensor [{B},{V},N,{self.J},4] on {f.device} (what "
@@ -102,6 +118,13 @@ class PoseOverlay:
                               or tuple(c.shape) != (B, N, self.J) or not c.is_contiguous()):
             raise capi.FvpError(f"joint_conf must be a contiguous float32 tensor [{B},{N},{self.J}] on {f.device}")
         stream = C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream) if f.device.type == "cuda" else None
+        if nv12:
+            rc = self.lib.fvp_draw_poses_nv12(_ptr(f.y), _ptr(f.uv), B, V, Hs, Ws, f.y_pitch, f.uv_pitch, f.y_frame_stride,
+                                              f.uv_frame_stride, f.standard, _ptr(v), _ptr(ids), _ptr(c), N, self.J,
+                                              self._limbs, len(self.limbs), self._palette, len(self.palette),
+                                              self.joint_radius_q4, self.limb_half_q4, self.alpha, self.conf_min, stream)
+            capi.check(self.lib, rc, "fvp_draw_poses_nv12")
+            return frames
         rc = self.lib.fvp_draw_poses(_ptr(f), B, V, Hs, Ws, _ptr(v), _ptr(ids), _ptr(c), N, self.J, self._limbs,
                                      len(self.limbs), self._palette, len(self.palette), self.joint_radius_q4,
                                      self.limb_half_q4, self.alpha, self.conf_min, stream)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 14
+#define FVP_ABI_VERSION 15
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -473,14 +473,60 @@ int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int Hs, int Ws, 
  * outside [0, J); alpha outside [1, 256]; joint_radius_q4 or limb_half_q4 outside [0, 1024]; NaN conf_min.
  * FVP_ELIMIT: N > 32, J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS, L > 64, P > 64, Hs or Ws > 16384, B * V > 65535 (one grid
  * plane per frame).  Nothing is written when an error is returned.  B * V == 0 returns 0 without a launch.
- * No bit-compatibility with OpenCV's rasteriser is claimed.  Not built: NV12 output, text labels, anti-aliasing, pitched
- * frames. */
+ * No bit-compatibility with OpenCV's rasteriser is claimed.  NV12 surfaces: fvp_draw_poses_nv12 below.  Not built: text
+ * labels, anti-aliasing, pitched RGB frames. */
 int fvp_draw_poses(uint8_t* frames /* [B*V][Hs][Ws][3], in place */, int B, int V, int Hs, int Ws,
                    const float* views /* [B][V][N][J][4] of fvp_joint_evidence */,
                    const int32_t* ids /* [B][N] or NULL */, const float* joint_conf /* [B][N][J] or NULL */,
                    int N, int J, const int32_t* limbs /* HOST [L][2], may be NULL when L == 0 */, int L,
                    const uint8_t* palette /* HOST [P][3] */, int P,
                    int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s);
+
+/* ---- skeleton overlay on NV12 surfaces (ABI 15) -------------------------------------------------------------------------
+ * fvp_draw_poses for the surface fvp_ingest_nv12 reads, in place, with no RGB frame in between.  y, uv, y_pitch, uv_pitch,
+ * y_frame_stride, uv_frame_stride (bytes) and standard are those of fvp_ingest_nv12: Hs x Ws luma bytes and Hs/2 x Ws/2
+ * interleaved (U, V) pairs per frame, Hs and Ws even, uv at an even address; frame b*V + v belongs to views[b][v].  views,
+ * ids, joint_conf, limbs, joint_radius_q4, limb_half_q4, alpha and conf_min are those of fvp_draw_poses.  THE CALLER
+ * GUARANTEES THAT THE TWO PLANES DO NOT OVERLAP (any frame of one with any frame of the other, padding aside).
+ * Coverage: drawable joints, drawn persons, Q4 geometry, the disc and the capsule test are exactly those of fvp_draw_poses;
+ *   person n covers luma pixel (x, y) iff one of its primitives covers the pixel centre (16x, 16y).  No new geometry.
+ * Colour: palette [P][3] is R, G, B in HOST memory.  Each entry is converted once, on the host, in int32:
+ *     Yc = clip(0, 255, YOFF + ((CYR*R + CYG*G + CYB*B + 32768) >> 16))          (>> is arithmetic: floor)
+ *     Uc = clip(0, 255, UOFF + ((CUR*R + CUG*G + CUB*B + 32768) >> 16))
+ *     Vc = clip(0, 255, VOFF + ((CVR*R + CVG*G + CVB*B + 32768) >> 16))
+ *   with the twelve constants of the standard below: the offsets, and round(k * 2^16) of the float64 values
+ *     luma (Kr, Kg, Kb) * sy;   U (-Kr, -Kg, 1-Kb) / (2 (1-Kb)) * sc;   V (1-Kr, -Kg, -Kb) / (2 (1-Kr)) * sc
+ *   (Kg = 1 - Kr - Kb; limited range: sy = 219/255, sc = 224/255, YOFF 16; full range: sy = sc = 1, YOFF 0; UOFF = VOFF =
+ *   128; Kr, Kb as for fvp_ingest_nv12).  Over all 2^24 colours limited range gives Y in 16..235 and U, V in 16..240
+ *   without the clip; full range reaches 256 on U (pure blue) and V (pure red): there the clip is part of the definition.
+ * Luma paint: for n = 0 .. N-1 ascending: if person n covers the pixel, ONCE per person
+ *     Y = (Yc * alpha + Y * (256 - alpha) + 128) >> 8.
+ * Chroma paint: the sample (cx, cy) serves the luma quad (2cx .. 2cx+1, 2cy .. 2cy+1).  With k_n in 0..4 the number of the
+ *   quad's pixels person n covers: for n ascending with k_n > 0, ONCE per person, a = alpha * k_n (1..1024):
+ *     U = (Uc * a + U * (1024 - a) + 512) >> 10        V = (Vc * a + V * (1024 - a) + 512) >> 10.
+ *   A partly covered quad takes the colour in proportion (a box filter); alpha = 256 and k = 4 write Uc, Vc exactly.
+ * Never read and never written: a luma byte nothing covers; a (U, V) pair whose quad has every k_n = 0; every byte of pitch
+ *   padding and between frames.
+ * One workgroup per 64 x 16 luma tile (32 x 8 chroma samples) of one frame, one thread per quad: tiles start at even
+ * coordinates, no two workgroups touch the same byte, the result does not depend on scheduling.  A (U, V) pair is one
+ * 2-byte load and one 2-byte store; luma goes byte by byte, nothing is required of y's alignment.
+ * FVP_EINVAL: as fvp_draw_poses (null y or uv for null frames), and: odd Hs or Ws; y_pitch < Ws or uv_pitch < Ws; odd uv
+ * address, uv_pitch or uv_frame_stride; unknown standard; with B * V > 1, y_frame_stride < (Hs-1) * y_pitch + Ws or
+ * uv_frame_stride < (Hs/2-1) * uv_pitch + Ws.  FVP_ELIMIT as fvp_draw_poses.  Nothing is written when an error is
+ * returned.  B * V == 0 returns 0 without a launch.  Not built: text labels, anti-aliasing, planar (I420) or 10-bit (P010)
+ * surfaces. */
+/*                                          YOFF  CYR    CYG    CYB  UOFF   CUR     CUG    CUB  VOFF   CVR    CVG    CVB */
+#define FVP_RGB2YUV_BT601_LIMITED_COEFFS { 16, 16829, 33039, 6416, 128, -9714, -19071, 28784, 128, 28784, -24103, -4681 }
+#define FVP_RGB2YUV_BT709_LIMITED_COEFFS { 16, 11966, 40254, 4064, 128, -6596, -22189, 28784, 128, 28784, -26145, -2639 }
+#define FVP_RGB2YUV_BT601_FULL_COEFFS { 0, 19595, 38470, 7471, 128, -11058, -21710, 32768, 128, 32768, -27439, -5329 }
+#define FVP_RGB2YUV_BT709_FULL_COEFFS { 0, 13933, 46871, 4732, 128, -7509, -25259, 32768, 128, 32768, -29763, -3005 }
+int fvp_draw_poses_nv12(uint8_t* y, uint8_t* uv /* in place */, int B, int V, int Hs, int Ws, long y_pitch, long uv_pitch,
+                        long y_frame_stride, long uv_frame_stride, /* bytes */
+                        int standard /* FVP_YUV_* */, const float* views /* [B][V][N][J][4] */,
+                        const int32_t* ids /* [B][N] or NULL */, const float* joint_conf /* [B][N][J] or NULL */,
+                        int N, int J, const int32_t* limbs /* HOST [L][2], may be NULL when L == 0 */, int L,
+                        const uint8_t* palette /* HOST [P][3], R G B */, int P,
+                        int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

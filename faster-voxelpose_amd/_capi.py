@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 15           # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 16           # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -87,6 +87,10 @@ SIGNATURES = {
                        _F, _P],
     "fvp_draw_poses_nv12": [_P, _P, _I, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, _P, _P, _P, _I, _I,
                             C.POINTER(C.c_int32), _I, C.POINTER(C.c_uint8), _I, _I, _I, _I, _F, _P],
+    "fvp_person_rois": [_P, _P, _P, _I, _I, _I, _I, C.c_uint32, _I, _F, _F, _F, _F, _P, _P, _P, _P],
+    "fvp_crop_rois": [_P, _I, _I, _I, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _I, _I, _I, _P, _P, _P],
+    "fvp_crop_rois_nv12": [_P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, _P, _I, _I, C.POINTER(_F),
+                           C.POINTER(_F), _I, _I, _P, _P, _P],
     "fvp_bb_input": [_P, _P, _I, _I, _I, _I, _P],
     "fvp_bb_pack": [_P, _P, _P, _P, _P, _P, _F, C.POINTER(FvpBbOp), _P, _P, _P],
     "fvp_bb_run": [C.POINTER(FvpBbOp), _I, _P, _P, C.POINTER(_P), _I, _I, _P, _I, _P, _P],

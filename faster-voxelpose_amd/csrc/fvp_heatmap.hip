@@ -483,6 +483,172 @@ k_draw_poses_nv12(uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, DrawNv12P
   *pc = uint16_t(unsigned(u) | (unsigned(v) << 8));
 }
 
+// ---- person crops out (fvp_person_rois, fvp_crop_rois, fvp_crop_rois_nv12; include/fvp.h, ABI 16) -----------------------
+// One box per (frame, view, person) from the per-view pixels of fvp_joint_evidence: one thread per box walks the person's
+// joints in ascending order (min / max of the usable ones, their count, the sum of their heatmap samples).  A few hundred
+// boxes of at most 32 joints: launch latency, nothing to tune.  A usable joint is a drawable joint of the overlay
+// (draw_joint's compares, restated on the floats) whose mask bit is set.
+struct RoiPrm {
+  uint32_t mask;
+  int min_joints;
+  float scale, pad_px, aspect, conf_min;
+};
+
+__global__ void __launch_bounds__(64)
+k_person_rois(const float* __restrict__ views, const int32_t* __restrict__ ids, const float* __restrict__ conf, int total,
+              int V, int N, int J, RoiPrm p, float* __restrict__ rois, int32_t* __restrict__ roi_count,
+              float* __restrict__ roi_score) {
+  const int i = blockIdx.x * 64 + threadIdx.x;          // box (f = b * V + v, n)
+  if (i >= total) return;
+  const int f = i / N, n = i - f * N, b = f / V;
+  const bool selected = !ids || ids[long(b) * N + n] >= 0;
+  int k = 0;
+  float xmin = 0.0f, xmax = 0.0f, ymin = 0.0f, ymax = 0.0f, sum = 0.0f;
+  if (selected) {
+    const float* vj = views + long(i) * J * 4;
+    const float* cj = conf ? conf + (long(b) * N + n) * J : nullptr;
+    for (int j = 0; j < J; ++j) {
+      if (!((p.mask >> j) & 1u)) continue;
+      const float px = vj[4 * j], py = vj[4 * j + 1], depth = vj[4 * j + 2];
+      bool ok = depth > 0.0f && fabsf(px) <= 32768.0f && fabsf(py) <= 32768.0f;
+      if (cj) ok = ok && cj[j] >= p.conf_min;
+      if (!ok) continue;
+      if (k == 0) {
+        xmin = xmax = px;
+        ymin = ymax = py;
+      } else {
+        xmin = px < xmin ? px : xmin;
+        xmax = px > xmax ? px : xmax;
+        ymin = py < ymin ? py : ymin;
+        ymax = py > ymax ? py : ymax;
+      }
+      sum = sum + vj[4 * j + 3];
+      ++k;
+    }
+  }
+  const bool valid = selected && k >= p.min_joints;
+  float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f, sc = 0.0f;
+  if (valid) {
+    const float cx = (xmin + xmax) * 0.5f, cy = (ymin + ymax) * 0.5f;
+    float hw = ((xmax - xmin) * 0.5f) * p.scale + p.pad_px, hh = ((ymax - ymin) * 0.5f) * p.scale + p.pad_px;
+    if (hw < hh * p.aspect)
+      hw = hh * p.aspect;
+    else
+      hh = __fdiv_rn(hw, p.aspect);
+    r0 = cx - hw;
+    r1 = cy - hh;
+    r2 = cx + hw;
+    r3 = cy + hh;
+    sc = __fdiv_rn(sum, float(k));
+  }
+  if (rois) {
+    float* o = rois + long(i) * 4;
+    o[0] = r0;
+    o[1] = r1;
+    o[2] = r2;
+    o[3] = r3;
+  }
+  if (roi_count) roi_count[i] = valid ? k : 0;
+  if (roi_score) roi_score[i] = sc;
+}
+
+// Crop + resize: ROI r (blockIdx.x, a grid dimension of its own) of frame r / rois_per_frame -> an h x w patch.  The ROI's
+// four floats and the matrix derived from them are the same for every lane of the workgroup (scalar loads), and from the
+// matrix on the arithmetic IS ingest_pair: one lane per destination pixel pair, one 16-byte store.  A workgroup of a
+// non-croppable ROI stores zeros and returns before any frame address is formed.
+__device__ __forceinline__ bool crop_matrix(const float* __restrict__ rois, int r, int h, int w, float (&inv)[6]) {
+  const float x0 = rois[4 * long(r)], y0 = rois[4 * long(r) + 1], x1 = rois[4 * long(r) + 2], y1 = rois[4 * long(r) + 3];
+  const float big = 3.402823466e+38f;                    // FLT_MAX: a NaN or an Inf fails the compare
+  if (!(fabsf(x0) <= big && fabsf(y0) <= big && fabsf(x1) <= big && fabsf(y1) <= big && x1 > x0 && y1 > y0)) return false;
+  const float ax = __fdiv_rn(x1 - x0, float(w)), ay = __fdiv_rn(y1 - y0, float(h));
+  inv[0] = ax;
+  inv[1] = 0.0f;
+  inv[2] = (x0 + 0.5f * ax) - 0.5f;                      // pixel centres map to pixel centres
+  inv[3] = 0.0f;
+  inv[4] = ay;
+  inv[5] = (y0 + 0.5f * ay) - 0.5f;
+  return true;
+}
+
+__device__ __forceinline__ void crop_zero_pair(int h, int w, int r, int y, int xp, uint16_t* __restrict__ nhwc8,
+                                               float* __restrict__ nchw) {
+  if (nchw) {
+    const long hw = long(h) * w;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float* o = nchw + (long(r) * 3 + c) * hw + long(y) * w + 2 * xp;
+      o[0] = 0.0f;
+      o[1] = 0.0f;
+    }
+  }
+  if (nhwc8) *reinterpret_cast<IngestB16*>(nhwc8 + ((long(r) * h + y) * (w / 2) + xp) * 8) = IngestB16{{0u, 0u, 0u, 0u}};
+}
+
+struct CropNorm {
+  float mean[3], stdv[3];
+};
+
+__global__ void __launch_bounds__(256)
+k_crop_rois(const uint8_t* __restrict__ frames, int Hs, int Ws, const float* __restrict__ rois, int rpf, CropNorm nm, int h,
+            int w, int swap, uint16_t* __restrict__ nhwc8, float* __restrict__ nchw) {
+  const int r = blockIdx.x;                              // the ROI: uniform over the workgroup
+  const int i = int(blockIdx.y) * 256 + threadIdx.x;     // one thread per pixel PAIR of the patch
+  const int w2 = w / 2;
+  if (i >= h * w2) return;
+  const int y = i / w2, xp = i - y * w2;
+  IngestPrm p;
+  if (!crop_matrix(rois, r, h, w, p.inv)) {
+    crop_zero_pair(h, w, r, y, xp, nhwc8, nchw);
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.mean[c] = nm.mean[c];
+    p.stdv[c] = nm.stdv[c];
+  }
+  const uint8_t* f = frames + long(r / rpf) * Hs * Ws * 3;
+  const int c0 = swap ? 2 : 0, c2 = 2 - c0;
+  ingest_pair(p, Hs, Ws, h, w, r, y, xp, nhwc8, nchw, [&](int yy, int xx) {
+    const uint8_t* q = f + (long(yy) * Ws + xx) * 3;
+    draw_note_read(q);
+    return IngestPx{{float(q[c0]), float(q[1]), float(q[c2])}};
+  });
+}
+
+__global__ void __launch_bounds__(256)
+k_crop_rois_nv12(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, int Hs, int Ws, Nv12Prm q,
+                 const float* __restrict__ rois, int rpf, CropNorm nm, int h, int w, uint16_t* __restrict__ nhwc8,
+                 float* __restrict__ nchw) {
+  const int r = blockIdx.x;                              // the ROI: uniform over the workgroup
+  const int i = int(blockIdx.y) * 256 + threadIdx.x;     // one thread per pixel PAIR of the patch
+  const int w2 = w / 2;
+  if (i >= h * w2) return;
+  const int y = i / w2, xp = i - y * w2;
+  IngestPrm p;
+  if (!crop_matrix(rois, r, h, w, p.inv)) {
+    crop_zero_pair(h, w, r, y, xp, nhwc8, nchw);
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.mean[c] = nm.mean[c];
+    p.stdv[c] = nm.stdv[c];
+  }
+  const uint8_t* fy = yp + long(r / rpf) * q.y_frame;
+  const uint8_t* fuv = uvp + long(r / rpf) * q.uv_frame;
+  ingest_pair(p, Hs, Ws, h, w, r, y, xp, nhwc8, nchw, [&](int yy, int xx) {   // the tap of k_ingest_nv12
+    const uint8_t* pl = fy + long(yy) * q.y_pitch + xx;
+    const uint8_t* pc = fuv + long(yy >> 1) * q.uv_pitch + 2 * (xx >> 1);
+    draw_note_read(pl);
+    draw_note_read(pc);
+    const int luma = *pl;
+    const uint32_t wd = *reinterpret_cast<const uint16_t*>(pc);
+    const int c = luma > q.yoff ? luma - q.yoff : 0, d = int(wd & 0xffu) - 128, e = int(wd >> 8) - 128;
+    const int l = q.cy * c + (1 << 19);
+    return IngestPx{{ingest_clip8(l + q.crv * e), ingest_clip8(l + q.cgu * d + q.cgv * e), ingest_clip8(l + q.cbu * d)}};
+  });
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -630,5 +796,80 @@ extern "C" int fvp_draw_poses_nv12(uint8_t* y, uint8_t* uv, int B, int V, int Hs
   hipLaunchKernelGGL(k_draw_poses_nv12, dim3(ceil_div(Ws, kDrawTW), ceil_div(Hs, kDrawTH), unsigned(B * V)),
                      dim3(kDrawThreads), 0, as_stream(s), y, uv, q, V, Hs, Ws, views, ids, joint_conf, N, J, L, P, prm,
                      joint_radius_q4, limb_half_q4, alpha, conf_min);
+  return launch_status();
+}
+
+extern "C" int fvp_person_rois(const float* views, const int32_t* ids, const float* joint_conf, int B, int V, int N, int J,
+                               uint32_t joint_mask, int min_joints, float scale, float pad_px, float aspect, float conf_min,
+                               float* rois, int32_t* roi_count, float* roi_score, fvp_stream_t s) {
+  FVP_REQUIRE(views && (rois || roi_count || roi_score));
+  FVP_REQUIRE(B >= 0 && V >= 0 && N >= 1 && J >= 1 && min_joints >= 1);
+  // a NaN fails each of these compares
+  FVP_REQUIRE(scale > 0.0f && std::isfinite(scale) && pad_px >= 0.0f && std::isfinite(pad_px) && aspect > 0.0f &&
+              std::isfinite(aspect) && !std::isnan(conf_min));
+  FVP_LIMIT(N <= kDrawMaxN && J <= FVP_MAX_JOINTS && V <= FVP_MAX_VIEWS);
+  const long total = long(B) * V * N;
+  if (long(B) * V == 0) return 0;
+  FVP_LIMIT(total < (1l << 31));
+  const RoiPrm p = {joint_mask, min_joints, scale, pad_px, aspect, conf_min};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_person_rois, dim3(unsigned((total + 63) / 64)), dim3(64), 0, as_stream(s), views, ids, joint_conf,
+                     int(total), V, N, J, p, rois, roi_count, roi_score);
+  return launch_status();
+}
+
+// argument checks both crop exports share (those of the ingest calls, and the ROI list's)
+static int crop_args(int F, int Hs, int Ws, const float* rois, int R, int rois_per_frame, const float mean[3],
+                     const float stdv[3], int h, int w, const void* nhwc8, const void* nchw, CropNorm& nm) {
+  FVP_REQUIRE(rois && mean && stdv && (nhwc8 || nchw));
+  FVP_REQUIRE(F >= 0 && R >= 0 && Hs > 0 && Ws > 0 && h > 0 && w > 0 && w % 2 == 0);
+  FVP_REQUIRE(rois_per_frame >= 1 && long(R) == long(F) * rois_per_frame);
+  for (int c = 0; c < 3; ++c) {
+    FVP_REQUIRE(std::isfinite(mean[c]) && std::isfinite(stdv[c]) && stdv[c] != 0.0f);
+    nm.mean[c] = mean[c];
+    nm.stdv[c] = stdv[c];
+  }
+  return 0;
+}
+
+extern "C" int fvp_crop_rois(const uint8_t* frames, int F, int Hs, int Ws, const float* rois, int R, int rois_per_frame,
+                             const float mean[3], const float stdv[3], int h, int w, int flags, uint16_t* nhwc8,
+                             float* nchw, fvp_stream_t s) {
+  FVP_REQUIRE(frames);
+  CropNorm nm;
+  if (const int rc = crop_args(F, Hs, Ws, rois, R, rois_per_frame, mean, stdv, h, w, nhwc8, nchw, nm)) return rc;
+  FVP_REQUIRE((flags & ~FVP_INGEST_SWAP_RB) == 0);
+  if (R == 0) return 0;
+  FVP_LIMIT(Hs < (1 << 24) && Ws < (1 << 24) && h < (1 << 24) && w < (1 << 24));   // pixel indices exact in fp32
+  const long blocks = (long(h) * (w / 2) + 255) / 256;
+  FVP_LIMIT(blocks <= 65535);                            // grid: (ROI, blocks of 256 pixel pairs)
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_crop_rois, dim3(unsigned(R), unsigned(blocks)), dim3(256), 0, as_stream(s), frames, Hs, Ws, rois,
+                     rois_per_frame, nm, h, w, (flags & FVP_INGEST_SWAP_RB) ? 1 : 0, nhwc8, nchw);
+  return launch_status();
+}
+
+extern "C" int fvp_crop_rois_nv12(const uint8_t* y, const uint8_t* uv, int F, int Hs, int Ws, long y_pitch, long uv_pitch,
+                                  long y_frame_stride, long uv_frame_stride, int standard, const float* rois, int R,
+                                  int rois_per_frame, const float mean[3], const float stdv[3], int h, int w,
+                                  uint16_t* nhwc8, float* nchw, fvp_stream_t s) {
+  static const int coeffs[4][6] = {FVP_YUV_BT601_LIMITED_COEFFS, FVP_YUV_BT709_LIMITED_COEFFS, FVP_YUV_BT601_FULL_COEFFS,
+                                   FVP_YUV_BT709_FULL_COEFFS};
+  FVP_REQUIRE(y && uv);
+  CropNorm nm;
+  if (const int rc = crop_args(F, Hs, Ws, rois, R, rois_per_frame, mean, stdv, h, w, nhwc8, nchw, nm)) return rc;
+  FVP_REQUIRE(Hs % 2 == 0 && Ws % 2 == 0 && y_pitch >= Ws && uv_pitch >= Ws);
+  // a (U, V) pair is one 2-byte load
+  FVP_REQUIRE(uv_pitch % 2 == 0 && uv_frame_stride % 2 == 0 && reinterpret_cast<uintptr_t>(uv) % 2 == 0);
+  FVP_REQUIRE(standard >= 0 && standard < 4);
+  if (R == 0) return 0;
+  FVP_LIMIT(Hs < (1 << 24) && Ws < (1 << 24) && h < (1 << 24) && w < (1 << 24));   // pixel indices exact in fp32
+  const long blocks = (long(h) * (w / 2) + 255) / 256;
+  FVP_LIMIT(blocks <= 65535);                            // grid: (ROI, blocks of 256 pixel pairs)
+  const int* k = coeffs[standard];
+  const Nv12Prm q = {y_pitch, uv_pitch, y_frame_stride, uv_frame_stride, k[0], k[1], k[2], k[3], k[4], k[5]};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_crop_rois_nv12, dim3(unsigned(R), unsigned(blocks)), dim3(256), 0, as_stream(s), y, uv, Hs, Ws, q,
+                     rois, rois_per_frame, nm, h, w, nhwc8, nchw);
   return launch_status();
 }

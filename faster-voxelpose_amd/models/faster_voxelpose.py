@@ -16,6 +16,9 @@ joints and dropped-out tracks bridged by prediction; one more launch behind the 
 ``model.overlay = PoseOverlay(cfg)`` (utils/overlay.py; needs ``evidence`` and ``uint8`` camera frames as ``views``) makes it
 also draw the skeletons into the caller's frames, in place, coloured by track id when a tracker is set; built with
 ``nv12=True`` it also draws into ``Nv12Frames`` views, in the surface itself.
+``model.crops = PersonCrops(cfg)`` (utils/crops.py; needs ``evidence`` and ``uint8`` or ``Nv12Frames`` camera frames as
+``views``) makes it also leave ``model.last_crops = (patches [B,V,N,3,h,w], rois [B,V,N,4], count [B,V,N], score [B,V,N])`` -
+a normalised, fixed-size image patch of every person in every view, cut out before the overlay draws; two more launches.
 """
 import time
 
@@ -65,6 +68,14 @@ class FasterVoxelPoseNet(nn.Module):
         # None: no launch more than without it.
         self.overlay = None
         self.last_overlay_views = None
+        # a utils.crops.PersonCrops (needs `evidence` and uint8 camera frames or Nv12Frames as `views`): forward() also
+        # cuts a patch per (frame, view, person) out of the caller's frames behind the tracker and the smoother and BEFORE the
+        # overlay draws (clean pixels) - boxes from the pixels the overlay would draw (`last_evidence[0]`, or, with a smoother,
+        # the one extra joint_evidence() of `last_smooth[0]` in `last_overlay_views`, issued once for both), `last_tracks[0]` as
+        # ids and `last_evidence[1]` as joint_conf - and keeps (patches, rois, count, score) in `last_crops`; the returned
+        # tuple is the same either way.  None: no launch more than without it.
+        self.crops = None
+        self.last_crops = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -99,6 +110,15 @@ class FasterVoxelPoseNet(nn.Module):
                                     "(NV12 surfaces, float images and input_heatmaps alone leave nothing to draw on; "
                                     "PoseOverlay(..., nv12=True) draws into Nv12Frames views, in the surface itself)")
             canvas = views
+        source = None
+        if self.crops is not None:
+            if not self.evidence:
+                raise capi.FvpError("model.crops cuts around the pixels of model.last_evidence: set model.evidence = True too")
+            if not isinstance(views, Nv12Frames) and (not torch.is_tensor(views) or views.dtype != torch.uint8):
+                raise capi.FvpError("model.crops cuts the patches out of the camera frames: pass them as views, uint8 "
+                                    "[B,V,Hs,Ws,3] or Nv12Frames (float images and input_heatmaps alone leave nothing to "
+                                    "cut from)")
+            source = views
         if views is not None:
             nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]
             frames = not nv12 and views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
@@ -171,16 +191,19 @@ class FasterVoxelPoseNet(nn.Module):
                 conf = self.last_evidence[1] if self.evidence else None
                 self.last_smooth = self.smoother.update(fused_poses, self.last_tracks[0], self.last_tracks[1],
                                                         joint_conf=conf, sequences=fs)
-        if canvas is not None:
+        if canvas is not None or source is not None:
             # ingest has read the frames on this stream already.  With a smoother the picture shows the steady poses:
-            # their pixels are one more evidence launch on the staging copy of this forward
+            # their pixels are one more evidence launch on the staging copy of this forward, shared by crops and overlay
             px, self.last_overlay_views = self.last_evidence[0], None
             if self.smoother is not None:
                 px = self.engine.joint_evidence(self.last_smooth[0], input_heatmaps, meta, cameras, resize_transform,
                                                 reuse_staging=True)[0]
                 self.last_overlay_views = px
-            self.overlay.draw(canvas, px, ids=self.last_tracks[0] if self.tracker is not None else None,
-                              joint_conf=self.last_evidence[1])
+            ids = self.last_tracks[0] if self.tracker is not None else None
+            if source is not None:                        # before the overlay paints: the patches hold clean pixels
+                self.last_crops = self.crops(source, px, ids=ids, joint_conf=self.last_evidence[1])
+            if canvas is not None:
+                self.overlay.draw(canvas, px, ids=ids, joint_conf=self.last_evidence[1])
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -244,7 +267,8 @@ class PipelinedForward:
     ``ids, slots, _ = tracker.update(outputs[0], meta)`` followed by ``smoother.update(outputs[0], ids, slots, meta=meta)``
     (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated).  A ``model.overlay`` is
     refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
-    ``model.joint_evidence``."""
+    ``model.joint_evidence``.  So is a ``model.crops``: ``crops(frames, views, ids)`` on the consumer stream, before any
+    ``overlay.draw``."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -267,6 +291,10 @@ class PipelinedForward:
         if model.overlay is not None:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.overlay = None "
                                 "and call overlay.draw(frames, views, ids) on the consumer stream")
+        if model.crops is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.crops = None "
+                                "and call crops(frames, views, ids) on the consumer stream, with views from "
+                                "model.joint_evidence(outputs[0], ...)[0], before any overlay.draw")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):
@@ -330,7 +358,8 @@ class GraphedPipeline:
     feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, a tracker
     stays outside: ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after ``event.wait()``
     (before the slot comes round again), and ``smoother.update(outputs[0], ids, slots, meta=meta)`` behind it; an overlay
-    likewise (``overlay.draw(frames, views, ids)`` on the consumer stream)."""
+    likewise (``overlay.draw(frames, views, ids)`` on the consumer stream), and person crops (``crops(frames, views, ids)``
+    there, before the overlay draws)."""
 
     def __init__(self, model, depth, meta, input_heatmaps, cameras, resize_transform, streams=None, warmup=2):
         self.pipe = PipelinedForward(model, depth=depth, streams=streams)

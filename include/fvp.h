@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 15
+#define FVP_ABI_VERSION 16
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -527,6 +527,72 @@ int fvp_draw_poses_nv12(uint8_t* y, uint8_t* uv /* in place */, int B, int V, in
                         int N, int J, const int32_t* limbs /* HOST [L][2], may be NULL when L == 0 */, int L,
                         const uint8_t* palette /* HOST [P][3], R G B */, int P,
                         int joint_radius_q4, int limb_half_q4, int alpha, float conf_min, fvp_stream_t s);
+
+/* ---- person crops out (ABI 16): per-view person boxes, and crop + resize + normalise in one pass ------------------------
+ * What a rig does with a person after the pose - appearance features, a top-down 2-D refiner, face blurring, an action
+ * classifier - starts from a fixed-size, normalised image patch of that person in the view that sees them best.
+ * fvp_person_rois turns the per-view pixels of fvp_joint_evidence into one box per (frame, view, person);
+ * fvp_crop_rois / fvp_crop_rois_nv12 cut any list of boxes out of the camera frames with the ingest's arithmetic.
+ *
+ * fvp_person_rois.  views [B][V][N][J][4], ids [B][N] or NULL, joint_conf [B][N][J] or NULL and conf_min are those of
+ * fvp_draw_poses.  joint_mask: bit j selects joint j (bits >= J are ignored).
+ * Usable joint (b,v,n,j): bit j of joint_mask is set and the joint is drawable by fvp_draw_poses' rule: depth > 0, |px| <=
+ *   32768 and |py| <= 32768 (fp32 compares: a NaN or an Inf fails them), and joint_conf is NULL or joint_conf[b][n][j] >=
+ *   conf_min (a NaN confidence is not usable).
+ * Selected person: ids is NULL or ids[b][n] >= 0.   k = the number of usable joints of (b,v,n).
+ * The box is VALID iff the person is selected and k >= min_joints.  For a valid box, with xmin, xmax, ymin, ymax the exact
+ * minimum / maximum of px, py over the usable joints (taken in ascending j: the first usable value, replaced by a later one
+ * iff that compares < resp. >), in fp32, every operation rounded on its own, IEEE division:
+ *     cx = (xmin + xmax) * 0.5f                          cy = (ymin + ymax) * 0.5f
+ *     hw = ((xmax - xmin) * 0.5f) * scale + pad_px       hh = ((ymax - ymin) * 0.5f) * scale + pad_px
+ *     if (hw < hh * aspect) hw = hh * aspect; else hh = hw / aspect;              (aspect = width / height of the crop)
+ *     roi = (cx - hw, cy - hh, cx + hw, cy + hh)         pixels of the ORIGINAL frame, NOT clipped to the frame
+ * A single usable joint with pad_px = 0 gives a degenerate box (x1 == x0), which fvp_crop_rois answers with zeros.
+ * Outputs, every element written by every call; each may be NULL, not all three:
+ *     rois      [B][V][N][4] fp32 (x0, y0, x1, y1);
+ *     roi_count [B][V][N]    int32 = k;
+ *     roi_score [B][V][N]    fp32 = (s summed over the usable joints in ascending j, from 0) / float(k), s = views[...][3]:
+ *                            the mean heatmap support of the box's joints in that view - argmax over V picks the best view.
+ * An invalid box writes zeros to all three.
+ * FVP_EINVAL: null views or all three outputs null; B or V < 0; N, J or min_joints < 1; scale not > 0, pad_px not >= 0,
+ * aspect not > 0, any of them not finite; NaN conf_min.  FVP_ELIMIT: N > 32, J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS.  Nothing
+ * is written when an error is returned.  B * V == 0 returns 0 without a launch.  One thread per box. */
+int fvp_person_rois(const float* views /* [B][V][N][J][4] of fvp_joint_evidence */, const int32_t* ids /* [B][N] or NULL */,
+                    const float* joint_conf /* [B][N][J] or NULL */, int B, int V, int N, int J, uint32_t joint_mask,
+                    int min_joints, float scale, float pad_px, float aspect, float conf_min,
+                    float* rois /* [B][V][N][4] */, int32_t* roi_count /* [B][V][N] */, float* roi_score /* [B][V][N] */,
+                    fvp_stream_t s);
+
+/* fvp_crop_rois / fvp_crop_rois_nv12: a generic crop-and-resize, any caller-made boxes.  The frames are those of
+ * fvp_ingest_frames ([F][Hs][Ws][3] uint8, flags = 0 or FVP_INGEST_SWAP_RB) resp. fvp_ingest_nv12 (y, uv, pitches, frame
+ * strides, standard).  rois [R][4] fp32 (x0, y0, x1, y1) in DEVICE memory, in pixels of the frame; ROI r reads frame
+ * r / rois_per_frame, and R == F * rois_per_frame.  mean, stdv [3]: HOST memory, by value, OUTPUT channel order.  The crop is
+ * h rows of w pixels, w even.  Outputs as the ingest's, one image per ROI (either may be NULL, not both):
+ *     nhwc8 [R][h][w/2] pixel pairs of 8 bf16, channel 3 = 0;      nchw [R][3][h][w] fp32.
+ * ROI r is CROPPABLE iff its four values are finite (fabsf <= FLT_MAX) and x1 > x0 and y1 > y0.  For a croppable ROI, in the
+ * kernel, fp32, every operation rounded on its own, IEEE division:
+ *     ax = (x1 - x0) / float(w)      bx = (x0 + 0.5f * ax) - 0.5f          (pixel centres map to pixel centres)
+ *     ay = (y1 - y0) / float(h)      by = (y0 + 0.5f * ay) - 0.5f
+ *     inv = { ax, 0, bx,   0, ay, by }
+ * and from there on the arithmetic is that of fvp_ingest_frames (resp. fvp_ingest_nv12) exactly: sx = inv[0]*x + inv[1]*y +
+ * inv[2], sy likewise, floor, four taps with a zero border (a tap outside the frame is 0 and, for NV12, is not converted),
+ * the same bilinear expression, / 255, - mean, / stdv, bf16 round-to-nearest-even.  Hence:
+ * CROP r EQUALS, BIT FOR BIT, fvp_ingest_frames (RESP. fvp_ingest_nv12) ON FRAME r / rois_per_frame WITH THAT inv, H = h, W = w.
+ * A non-croppable ROI writes an all-zero image (fp32 0, bf16 0) and loads no frame byte.  No byte outside a frame's pixels -
+ * pitch padding, the gap between frames - is ever read.  A crop that shrinks by more than 2 x aliases as the ingest does.
+ * One workgroup handles 256 pixel pairs of ONE ROI (the ROI is a grid dimension): the four floats and inv are wave-uniform.
+ * FVP_EINVAL: as fvp_ingest_frames / fvp_ingest_nv12 (inv aside), and: null rois; F or R < 0; rois_per_frame < 1; R != F *
+ * rois_per_frame; a flag other than FVP_INGEST_SWAP_RB.  FVP_ELIMIT: as the ingest calls; more than 65535 * 256 pixel pairs
+ * per crop.  Nothing is written when an error is returned.  R == 0 returns 0 without a launch.  Not built: rotated boxes,
+ * anti-aliased down-scaling, I420 / P010 surfaces, compaction of the valid crops. */
+int fvp_crop_rois(const uint8_t* frames /* [F][Hs][Ws][3] */, int F, int Hs, int Ws, const float* rois /* DEVICE [R][4] */,
+                  int R, int rois_per_frame, const float mean[3], const float stdv[3], int h, int w, int flags,
+                  uint16_t* nhwc8 /* [R][h][w/2][8] */, float* nchw /* [R][3][h][w] */, fvp_stream_t s);
+int fvp_crop_rois_nv12(const uint8_t* y, const uint8_t* uv, int F, int Hs, int Ws, long y_pitch, long uv_pitch,
+                       long y_frame_stride, long uv_frame_stride, /* bytes */
+                       int standard /* FVP_YUV_* */, const float* rois /* DEVICE [R][4] */, int R, int rois_per_frame,
+                       const float mean[3], const float stdv[3], int h, int w, uint16_t* nhwc8, float* nchw,
+                       fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

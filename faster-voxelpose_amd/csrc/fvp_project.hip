@@ -15,6 +15,7 @@
 // neighbouring heatmap pixels and every store is a contiguous 256-byte row.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdlib>
 
 #include "fvp_common.h"
@@ -129,6 +130,118 @@ k_joint_evidence(const float* __restrict__ heat_cl, const Cam* __restrict__ cams
       reinterpret_cast<float4*>(views)[((size_t(b) * g.V + v) * N + n) * J + j] = make_float4(px, py, depth, s);
   }
   if (conf) conf[i] = clampf(__fdiv_rn(acc, float(g.V)), 0.0f, 1.0f);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Joint visibility per view (fvp_joint_visibility, include/fvp.h): the ray from the camera centre to a joint against the
+// capsule model of every present person of the frame.  One workgroup per (frame, person slot): the frame's N*J joints
+// (w = 1 iff finite) and the presence flags are staged in LDS, thread t < V*J owns (v, j) = (t / J, t % J) and walks the
+// persons and primitives in order - every LDS read and every table read (the table is a kernel argument) is uniform over
+// the workgroup.  Per-view results go through LDS; thread j < J sums the seeing views in ascending v.  No atomics.
+struct VisPrims {
+  int n;
+  int ik[FVP_VIS_MAX_PRIMS];        // i | k << 8
+  float r[FVP_VIS_MAX_PRIMS];
+};
+
+__device__ __forceinline__ float dot3(float p0, float p1, float p2, float q0, float q1, float q2) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(p0, q0), __fmul_rn(p1, q1)), __fmul_rn(p2, q2));
+}
+
+__global__ void __launch_bounds__(256)
+k_joint_visibility(const float* __restrict__ fused, const Cam* __restrict__ cams, const int* __restrict__ frame_set,
+                   const int* __restrict__ ids, const float* __restrict__ views, int V, int N, int J, VisPrims prm,
+                   float guard, float xmax, float ymax, int* __restrict__ occluder, float* __restrict__ vis_conf,
+                   int* __restrict__ vis_count) {
+  __shared__ float4 pose[FVP_VIS_MAX_PEOPLE * FVP_MAX_JOINTS];
+  __shared__ int present[FVP_VIS_MAX_PEOPLE];
+  __shared__ float seen_s[FVP_MAX_VIEWS * FVP_MAX_JOINTS];
+  __shared__ int seen[FVP_MAX_VIEWS * FVP_MAX_JOINTS];
+  const int b = blockIdx.x / N, n = blockIdx.x - b * N;
+  const int tid = threadIdx.x;
+  const float* frame = fused + size_t(b) * N * J * 5;
+  for (int q = tid; q < N * J; q += 256) {
+    const float x = frame[q * 5 + 0], y = frame[q * 5 + 1], z = frame[q * 5 + 2];
+    const bool fin = fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX;
+    pose[q] = make_float4(x, y, z, fin ? 1.0f : 0.0f);
+  }
+  if (tid < N) present[tid] = frame[tid * J * 5 + 3] >= 0.0f && (!ids || ids[b * N + tid] >= 0);
+  __syncthreads();
+  const int v = tid / J, j = tid - v * J;
+  if (v < V) {
+    const Cam& cm = cams[size_t(frame_set[b]) * V + v];
+    const float c0 = cm.T[0], c1 = cm.T[1], c2 = cm.T[2];
+    const float4 P = pose[n * J + j];
+    const float d10 = __fsub_rn(P.x, c0), d11 = __fsub_rn(P.y, c1), d12 = __fsub_rn(P.z, c2);
+    const float a = dot3(d10, d11, d12, d10, d11, d12);
+    const float len = sqrtf(a);
+    int occ = -2;
+    if (present[n] && P.w != 0.0f && len > guard) {
+      const float smax = __fsub_rn(1.0f, __fdiv_rn(guard, len));
+      float best = 0.0f;
+      occ = -1;
+      for (int m = 0; m < N; ++m) {
+        if (!present[m]) continue;
+        for (int l = 0; l < prm.n; ++l) {
+          const int pi = prm.ik[l] & 255, pk = prm.ik[l] >> 8;
+          const float4 A = pose[m * J + pi], Bq = pose[m * J + pk];
+          if (A.w == 0.0f || Bq.w == 0.0f || (m == n && (pi == j || pk == j))) continue;
+          const float d20 = __fsub_rn(Bq.x, A.x), d21 = __fsub_rn(Bq.y, A.y), d22 = __fsub_rn(Bq.z, A.z);
+          const float r00 = __fsub_rn(c0, A.x), r01 = __fsub_rn(c1, A.y), r02 = __fsub_rn(c2, A.z);
+          const float e = dot3(d20, d21, d22, d20, d21, d22);
+          const float f = dot3(d20, d21, d22, r00, r01, r02);
+          const float c = dot3(d10, d11, d12, r00, r01, r02);
+          float sv, tv;
+          if (e == 0.0f) {
+            tv = 0.0f;
+            sv = clampf(__fdiv_rn(-c, a), 0.0f, smax);
+          } else {
+            const float bb = dot3(d10, d11, d12, d20, d21, d22);
+            const float den = __fsub_rn(__fmul_rn(a, e), __fmul_rn(bb, bb));
+            sv = den > 0.0f ? clampf(__fdiv_rn(__fsub_rn(__fmul_rn(bb, f), __fmul_rn(c, e)), den), 0.0f, smax) : 0.0f;
+            tv = __fdiv_rn(__fadd_rn(__fmul_rn(bb, sv), f), e);
+            if (tv < 0.0f) {
+              tv = 0.0f;
+              sv = clampf(__fdiv_rn(-c, a), 0.0f, smax);
+            } else if (tv > 1.0f) {
+              tv = 1.0f;
+              sv = clampf(__fdiv_rn(__fsub_rn(bb, c), a), 0.0f, smax);
+            }
+          }
+          const float w0 = __fsub_rn(__fadd_rn(c0, __fmul_rn(d10, sv)), __fadd_rn(A.x, __fmul_rn(d20, tv)));
+          const float w1 = __fsub_rn(__fadd_rn(c1, __fmul_rn(d11, sv)), __fadd_rn(A.y, __fmul_rn(d21, tv)));
+          const float w2 = __fsub_rn(__fadd_rn(c2, __fmul_rn(d12, sv)), __fadd_rn(A.z, __fmul_rn(d22, tv)));
+          const float rr = __fmul_rn(prm.r[l], prm.r[l]);
+          // persons in ascending m and a strict compare: among equal s the lowest slot stays
+          if (dot3(w0, w1, w2, w0, w1, w2) <= rr && (occ < 0 || sv < best)) {
+            best = sv;
+            occ = m;
+          }
+        }
+      }
+    }
+    const size_t o = ((size_t(b) * V + v) * N + n) * J + j;
+    if (occluder) occluder[o] = occ;
+    if (views) {
+      const float4 e4 = reinterpret_cast<const float4*>(views)[o];
+      seen[tid] = occ == -1 && e4.z > 0.0f && e4.x >= 0.0f && e4.x <= xmax && e4.y >= 0.0f && e4.y <= ymax;
+      seen_s[tid] = e4.w;
+    }
+  }
+  if (!views) return;                 // uniform: a kernel argument
+  __syncthreads();
+  if (tid < J) {
+    float sum = 0.0f;
+    int cnt = 0;
+    for (int u = 0; u < V; ++u)
+      if (seen[u * J + tid]) {
+        sum = __fadd_rn(sum, seen_s[u * J + tid]);
+        ++cnt;
+      }
+    const size_t o = (size_t(b) * N + n) * J + tid;
+    if (vis_conf) vis_conf[o] = cnt ? clampf(__fdiv_rn(sum, float(cnt)), 0.0f, 1.0f) : 0.0f;
+    if (vis_count) vis_count[o] = cnt;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -768,6 +881,34 @@ extern "C" int fvp_joint_evidence(const float* heat_cl, const float* cams, const
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_joint_evidence, dim3(ceil_div(B * N * g->J, 256)), dim3(256), 0, as_stream(s), heat_cl,
                      reinterpret_cast<const Cam*>(cams), frame_set, fused_poses, B, N, *g, views, joint_conf);
+  return launch_status();
+}
+
+extern "C" int fvp_joint_visibility(const float* fused_poses, const float* cams, const int32_t* frame_set,
+                                    const int32_t* ids, const float* views, int B, int V, int N, int J,
+                                    const int32_t* prims, const float* radius_mm, int L, float guard_mm, int Hs, int Ws,
+                                    int32_t* occluder, float* vis_conf, int32_t* vis_count, fvp_stream_t s) {
+  FVP_REQUIRE(fused_poses && cams && frame_set && ((prims && radius_mm) || L <= 0));
+  FVP_REQUIRE((occluder || vis_conf || vis_count) && (views || (!vis_conf && !vis_count)));
+  FVP_REQUIRE(B >= 0 && V >= 1 && N >= 1 && J >= 1 && Hs >= 1 && Ws >= 1 && L >= 0);
+  FVP_REQUIRE(guard_mm >= 0.0f && guard_mm <= FLT_MAX);          // a NaN fails
+  FVP_LIMIT(N <= FVP_VIS_MAX_PEOPLE && J <= FVP_MAX_JOINTS && V <= FVP_MAX_VIEWS && L <= FVP_VIS_MAX_PRIMS);
+  VisPrims prm;
+  prm.n = L;
+  for (int l = 0; l < FVP_VIS_MAX_PRIMS; ++l) {
+    prm.ik[l] = 0;
+    prm.r[l] = 0.0f;
+    if (l >= L) continue;
+    const int i = prims[2 * l], k = prims[2 * l + 1];
+    FVP_REQUIRE(i >= 0 && i < J && k >= 0 && k < J && radius_mm[l] > 0.0f && radius_mm[l] <= FLT_MAX);
+    prm.ik[l] = i | (k << 8);
+    prm.r[l] = radius_mm[l];
+  }
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_joint_visibility, dim3(B * N), dim3(256), 0, as_stream(s), fused_poses,
+                     reinterpret_cast<const Cam*>(cams), frame_set, ids, views, V, N, J, prm, guard_mm, float(Ws - 1),
+                     float(Hs - 1), occluder, vis_conf, vis_count);
   return launch_status();
 }
 

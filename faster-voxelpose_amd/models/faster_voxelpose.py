@@ -19,6 +19,9 @@ also draw the skeletons into the caller's frames, in place, coloured by track id
 ``model.crops = PersonCrops(cfg)`` (utils/crops.py; needs ``evidence`` and ``uint8`` or ``Nv12Frames`` camera frames as
 ``views``) makes it also leave ``model.last_crops = (patches [B,V,N,3,h,w], rois [B,V,N,4], count [B,V,N], score [B,V,N])`` -
 a normalised, fixed-size image patch of every person in every view, cut out before the overlay draws; two more launches.
+``model.visibility = JointVisibility(cfg)`` (utils/visibility.py; needs ``evidence``) makes it also leave
+``model.last_visibility = (occluder [B,V,N,J], vis_conf [B,N,J], vis_count [B,N,J])`` - which cameras see each joint past the
+other people's bodies, and the joint's confidence over those views only; one more launch behind the evidence's.
 """
 import time
 
@@ -76,6 +79,13 @@ class FasterVoxelPoseNet(nn.Module):
         # tuple is the same either way.  None: no launch more than without it.
         self.crops = None
         self.last_crops = None
+        # a utils.visibility.JointVisibility (needs `evidence`): forward() also tests every fused joint's line of sight to
+        # every camera against the other people's bodies, right behind the evidence launch, on `last_evidence[0]` and the
+        # engine's camera tables, and keeps (occluder, vis_conf, vis_count) in `last_visibility`.  Built with feeds_conf=True
+        # (the default), `vis_conf` takes the place of `last_evidence[1]` as the joint_conf of smoother, overlay and crops;
+        # the returned tuple is the same either way.  None: no launch more than without it.
+        self.visibility = None
+        self.last_visibility = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -99,6 +109,8 @@ class FasterVoxelPoseNet(nn.Module):
                                       "(call model.eval()); training losses are outside the hot path")
         if self.smoother is not None and self.tracker is None:
             raise capi.FvpError("model.smoother filters the tracks of model.tracker: set model.tracker (a PoseTracker) too")
+        if self.visibility is not None and not self.evidence:
+            raise capi.FvpError("model.visibility judges the pixels of model.last_evidence: set model.evidence = True too")
         canvas = None
         if self.overlay is not None:
             if not self.evidence:
@@ -176,6 +188,16 @@ class FasterVoxelPoseNet(nn.Module):
             # part of the captured graph and `last_evidence` holds static tensors, overwritten by the next replay
             self.last_evidence = self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform,
                                                             reuse_staging=True)
+        conf = self.last_evidence[1] if self.evidence else None
+        if self.visibility is not None:
+            # static-shape and sync-free as well: the body model travels by value, the camera tables are the engine's
+            vis = self.visibility
+            ws, hs = self.cfg.DATASET.ORI_IMAGE_SIZE
+            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
+            self.last_visibility = vis(fused_poses, self.engine.geo.cams, fs, views=self.last_evidence[0],
+                                       frame_size=vis.frame_size or (hs, ws))
+            if vis.feeds_conf:
+                conf = self.last_visibility[1]
         if self.tracker is not None:
             # the frames' sequence rows are the engine's own table (frame_sets: cached, no upload here); static-shape and
             # sync-free, so a captured graph holds the launch and the state in device memory carries from replay to replay
@@ -188,7 +210,6 @@ class FasterVoxelPoseNet(nn.Module):
                 if self.smoother.nseq < self.tracker.nseq:
                     raise capi.FvpError(f"model.smoother was built for nseq = {self.smoother.nseq}, model.tracker for "
                                         f"{self.tracker.nseq}")
-                conf = self.last_evidence[1] if self.evidence else None
                 self.last_smooth = self.smoother.update(fused_poses, self.last_tracks[0], self.last_tracks[1],
                                                         joint_conf=conf, sequences=fs)
         if canvas is not None or source is not None:
@@ -201,9 +222,9 @@ class FasterVoxelPoseNet(nn.Module):
                 self.last_overlay_views = px
             ids = self.last_tracks[0] if self.tracker is not None else None
             if source is not None:                        # before the overlay paints: the patches hold clean pixels
-                self.last_crops = self.crops(source, px, ids=ids, joint_conf=self.last_evidence[1])
+                self.last_crops = self.crops(source, px, ids=ids, joint_conf=conf)
             if canvas is not None:
-                self.overlay.draw(canvas, px, ids=ids, joint_conf=self.last_evidence[1])
+                self.overlay.draw(canvas, px, ids=ids, joint_conf=conf)
         # the channels-last staging copy is valid for this call only: a later tensor may reuse the
         # same address / version / shape once the caching allocator recycles the block
         self.engine.invalidate_staging()
@@ -268,7 +289,7 @@ class PipelinedForward:
     (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated).  A ``model.overlay`` is
     refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
     ``model.joint_evidence``.  So is a ``model.crops``: ``crops(frames, views, ids)`` on the consumer stream, before any
-    ``overlay.draw``."""
+    ``overlay.draw``.  And a ``model.visibility``: ``visibility(outputs[0], cameras, meta, views=views)`` there."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -295,6 +316,10 @@ class PipelinedForward:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.crops = None "
                                 "and call crops(frames, views, ids) on the consumer stream, with views from "
                                 "model.joint_evidence(outputs[0], ...)[0], before any overlay.draw")
+        if model.visibility is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.visibility = None "
+                                "and call visibility(outputs[0], cameras, meta, views=views) on the consumer stream, with "
+                                "views from model.joint_evidence(outputs[0], ...)[0]")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):

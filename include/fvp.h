@@ -26,12 +26,14 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 16
+#define FVP_ABI_VERSION 17
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
 #define FVP_TRACK_MAX_DETS 32   /* fvp_track_update: person slots per frame (N)   */
 #define FVP_TRACK_MAX_TRACKS 64 /* fvp_track_update: track slots per sequence (T) */
+#define FVP_VIS_MAX_PEOPLE 32   /* fvp_joint_visibility: person slots per frame (N) */
+#define FVP_VIS_MAX_PRIMS 64    /* fvp_joint_visibility: body primitives per person (L) */
 
 #define FVP_EINVAL 10001 /* bad argument (null pointer, unsupported size) */
 #define FVP_ELIMIT 10002 /* size beyond a compiled limit (see message) */
@@ -593,6 +595,62 @@ int fvp_crop_rois_nv12(const uint8_t* y, const uint8_t* uv, int F, int Hs, int W
                        int standard /* FVP_YUV_* */, const float* rois /* DEVICE [R][4] */, int R, int rois_per_frame,
                        const float mean[3], const float stdv[3], int h, int w, uint16_t* nhwc8, float* nchw,
                        fvp_stream_t s);
+
+/* ---- joint visibility per view (ABI 17): a device-side occlusion test ---------------------------------------------------
+ * fvp_joint_evidence says where a joint lands in every view and what the heatmap holds there, not whether the camera can see
+ * it: a joint behind another person's torso still projects into the frame.  With every person's 3-D skeleton and every
+ * camera centre in hand the answer is geometry: the ray from the camera centre to the joint is tested against a capsule model
+ * of every present person of the frame.
+ *
+ * fused_poses [B][N][J][5], cams [nsets][V][FVP_CAM_FLOATS] and frame_set [B] are those of fvp_joint_evidence; ids [B][N] int32
+ * (fvp_track_update) or NULL; views [B][V][N][J][4] of fvp_joint_evidence, or NULL.  Body model, HOST memory, passed to the
+ * kernel by value: prims [L][2] int32 joint index pairs, radius_mm [L].  Primitive (i, k, r) of a person is the capsule of radius r
+ * around the 3-D segment from joint i to joint k; i == k is a sphere (a head).
+ *
+ * fp32, every operation rounded on its own (no contraction), IEEE division and square root:
+ *   dot(p,q) = (p0*q0 + p1*q1) + p2*q2          clamp(x,lo,hi) = fminf(fmaxf(x,lo),hi)
+ *   person m of frame b is PRESENT iff fused_poses[b][m][0][3] >= 0 and (ids is NULL or ids[b][m] >= 0);
+ *   a point is FINITE iff fabsf(c) <= FLT_MAX for its three coordinates;
+ *   C = cams[frame_set[b]][v].T (floats 9..11 of the record): the camera centre, as in the projection, d = w - T.
+ * For joint (b,v,n,j), P = fused_poses[b][n][j][0:3]:
+ *   1. d1 = P - C, a = dot(d1,d1), len = sqrtf(a).  The joint is EVALUATED iff person n is present, P is finite and
+ *      len > guard_mm (a NaN fails); otherwise occluder = -2.  smax = 1.0f - guard_mm / len: the last guard_mm of the ray before
+ *      the joint are never tested, so the joint's own flesh does not hide it.
+ *   2. Candidates: the primitives (i,k,r) of every present person m, A = pose[m][i], B = pose[m][k].  A primitive is skipped
+ *      if A or B is not finite, or if m == n and (i == j or k == j): the limbs that end in the joint itself.
+ *   3. Closest points of the segments C + s*d1, s in [0,smax], and A + t*d2, t in [0,1] (Ericson, Real-Time Collision
+ *      Detection, 5.1.9): d2 = B - A, r0 = C - A, e = dot(d2,d2), f = dot(d2,r0), c = dot(d1,r0).
+ *        if e == 0:  t = 0, s = clamp(-c / a, 0, smax)
+ *        else:       bb = dot(d1,d2), den = a*e - bb*bb, s = den > 0 ? clamp((bb*f - c*e) / den, 0, smax) : 0,
+ *                    t = (bb*s + f) / e;
+ *                    if t < 0:       t = 0, s = clamp(-c / a, 0, smax)
+ *                    else if t > 1:  t = 1, s = clamp((bb - c) / a, 0, smax)
+ *      w = (C + d1*s) - (A + d2*t) per component.  HIT iff dot(w,w) <= r*r (a NaN fails).
+ *   4. No hit: occluder = -1, a free line of sight.  Otherwise occluder = m of the hit with the smallest (s, m) in
+ *      lexicographic order: the body nearest the camera.  m == n is self-occlusion.
+ *   5. With views: view v SEES joint (b,n,j) iff occluder == -1, depth > 0, 0 <= px <= Ws-1 and 0 <= py <= Hs-1 (fp32
+ *      compares against float(Ws-1), float(Hs-1); a NaN fails).  vis_count = the number of seeing views; vis_conf =
+ *      clamp((s_v summed over the seeing views in ascending v, from 0) / float(vis_count), 0, 1), 0 when the count is 0.  The
+ *      summation order is fixed: the result does not depend on scheduling.
+ * Outputs, every element of a non-NULL output written by every call; any may be NULL, not all three; vis_conf and vis_count
+ * need views:
+ *     occluder  [B][V][N][J] int32: -2 not evaluated, -1 visible, else the occluding person's slot;
+ *     vis_conf  [B][N][J]    fp32;        vis_count [B][N][J] int32.
+ * FVP_EINVAL: null fused_poses, cams or frame_set; prims or radius_mm null with L > 0; all outputs null; vis_conf or vis_count
+ * without views; B < 0; V, N, J, Hs or Ws < 1; L < 0; a primitive index outside [0,J); a radius not > 0 or not finite;
+ * guard_mm not >= 0 or not finite.  FVP_ELIMIT: N > FVP_VIS_MAX_PEOPLE, J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS, L >
+ * FVP_VIS_MAX_PRIMS.  Nothing is written when an error is returned.  B == 0 returns 0 without a launch.
+ * One launch, no host synchronisation, no atomics: one workgroup per (b, n) with the frame's joints in LDS, one thread per
+ * (v, j); the per-view results go through LDS and one thread per j sums the views in order.  Not built: occlusion by scene
+ * objects, soft visibility, a per-view mask inside fvp_draw_poses / fvp_person_rois. */
+int fvp_joint_visibility(const float* fused_poses /* [B][N][J][5] */, const float* cams /* [nsets][V][FVP_CAM_FLOATS] */,
+                         const int32_t* frame_set /* [B] */, const int32_t* ids /* [B][N] or NULL */,
+                         const float* views /* [B][V][N][J][4] of fvp_joint_evidence, or NULL */,
+                         int B, int V, int N, int J,
+                         const int32_t* prims /* HOST [L][2] */, const float* radius_mm /* HOST [L] */, int L,
+                         float guard_mm, int Hs, int Ws,
+                         int32_t* occluder /* [B][V][N][J] */, float* vis_conf /* [B][N][J] */,
+                         int32_t* vis_count /* [B][N][J] */, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

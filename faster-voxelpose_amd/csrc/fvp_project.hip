@@ -245,6 +245,288 @@ k_joint_visibility(const float* __restrict__ fused, const Cam* __restrict__ cams
 }
 
 // ---------------------------------------------------------------------------------------------
+// Triangulated joints from the views (fvp_triangulate_joints, include/fvp.h): the point the rays through the 2-D heatmap
+// peaks of the usable views agree on, its reprojection residual per view and the residual per camera.  One workgroup per
+// (frame, person slot); the set's camera records are staged in LDS once.  Thread t < V*J owns (v, j) = (t / J, t % J) for
+// steps 1-6 of the definition - the window around the reprojected fused joint, the peak, its sub-cell refinement, the
+// pixel in the original image, the undistorted ray - and leaves ray, weight, observation and state in LDS.  Thread j < J
+// then solves its joint's 3x3 normal equations in fp64 over the views in ascending order (named scalars: no indexed local
+// arrays, nothing in scratch), computes the residuals, runs the one rejection round and writes the per-joint outputs;
+// the (v, j) threads write obs and view_state.  No atomics.  Every window load lies inside the map: the loops run over the
+// window clipped to the map, and the centre is tested as a float before it becomes an int.
+struct TriParams {
+  float inv[6];                     // heat-map cell -> original pixel (the host's inverse, fp32)
+  int radius, iters, min_views, nsets;
+  float min_peak, reject_px;
+  double min_det;
+};
+
+__device__ __forceinline__ float tri_refine(float m, float c, float p) {
+  const float den = __fsub_rn(__fsub_rn(__fmul_rn(2.0f, c), m), p);
+  return den > 0.0f ? clampf(__fdiv_rn(__fmul_rn(0.5f, __fsub_rn(p, m)), den), -0.5f, 0.5f) : 0.0f;
+}
+
+// steps 1-6 for one (view, joint): the state, the ray (d, w) and the observation (ox, oy, peak, -1)
+__device__ __forceinline__ int tri_observe(const float* __restrict__ cl, const Cam& cm, const FvpGeom& g,
+                                           const TriParams& tp, float wx, float wy, float wz, float4& ray, float4& ob) {
+  if (!(fabsf(wx) <= FLT_MAX && fabsf(wy) <= FLT_MAX && fabsf(wz) <= FLT_MAX)) return FVP_TRI_OUTSIDE;
+  float px, py, depth;
+  project_pixel(cm, wx, wy, wz, px, py, depth);
+  if (!(depth > 0.0f)) return FVP_TRI_OUTSIDE;
+  const float ax = __fmaf_rn(g.rt[2], 1.0f, __fmaf_rn(g.rt[1], py, __fmul_rn(g.rt[0], px)));
+  const float ay = __fmaf_rn(g.rt[5], 1.0f, __fmaf_rn(g.rt[4], py, __fmul_rn(g.rt[3], px)));
+  const float hx = __fdiv_rn(__fmul_rn(ax, g.hm_w), g.img_w);
+  const float hy = __fdiv_rn(__fmul_rn(ay, g.hm_h), g.img_h);
+  if (!(fabsf(hx) <= FLT_MAX && fabsf(hy) <= FLT_MAX)) return FVP_TRI_OUTSIDE;
+  const float cxf = floorf(__fadd_rn(hx, 0.5f)), cyf = floorf(__fadd_rn(hy, 0.5f));
+  const int r = tp.radius, W = g.W, H = g.H, JP = g.JP;
+  // as floats, before any conversion: a centre whose window holds no cell of the map costs no load
+  if (!(cxf >= float(-r) && cxf <= float(W - 1 + r) && cyf >= float(-r) && cyf <= float(H - 1 + r))) return FVP_TRI_OUTSIDE;
+  const int cx = int(cxf), cy = int(cyf);
+  const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < W - 1 ? cx + r : W - 1;
+  const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < H - 1 ? cy + r : H - 1;
+  bool have = false;
+  float best = 0.0f;
+  int bx = 0, by = 0;
+  for (int y = y0; y <= y1; ++y)
+    for (int x = x0; x <= x1; ++x) {
+      const float val = cl[size_t(y * W + x) * JP];
+      // ascending (y, x) and a strict compare: a tie stays with the smallest (y, x); a NaN never wins
+      if (val == val && (!have || val > best)) {
+        have = true;
+        best = val;
+        bx = x;
+        by = y;
+      }
+    }
+  if (!have) return FVP_TRI_PEAK_LOW;
+  ob.z = best;
+  if (!(best >= tp.min_peak)) return FVP_TRI_PEAK_LOW;
+  if (bx == cx - r || bx == cx + r || by == cy - r || by == cy + r) return FVP_TRI_NOT_ENCLOSED;
+  // the winner is inside the map; a neighbour outside it counts as 0
+  const float xm = bx > 0 ? cl[size_t(by * W + bx - 1) * JP] : 0.0f;
+  const float xp = bx < W - 1 ? cl[size_t(by * W + bx + 1) * JP] : 0.0f;
+  const float ym = by > 0 ? cl[size_t((by - 1) * W + bx) * JP] : 0.0f;
+  const float yp = by < H - 1 ? cl[size_t((by + 1) * W + bx) * JP] : 0.0f;
+  const float qx = __fadd_rn(float(bx), tri_refine(xm, best, xp));
+  const float qy = __fadd_rn(float(by), tri_refine(ym, best, yp));
+  const float ox = __fmaf_rn(tp.inv[2], 1.0f, __fmaf_rn(tp.inv[1], qy, __fmul_rn(tp.inv[0], qx)));
+  const float oy = __fmaf_rn(tp.inv[5], 1.0f, __fmaf_rn(tp.inv[4], qy, __fmul_rn(tp.inv[3], qx)));
+  ob.x = ox;
+  ob.y = oy;
+  const float u0 = __fdiv_rn(__fsub_rn(ox, cm.c[0]), cm.f[0]), u1 = __fdiv_rn(__fsub_rn(oy, cm.c[1]), cm.f[1]);
+  float y0n = u0, y1n = u1;
+  for (int it = 0; it < tp.iters; ++it) {
+    const float rr = __fadd_rn(__fmul_rn(y0n, y0n), __fmul_rn(y1n, y1n));
+    float d = __fadd_rn(1.0f, __fmul_rn(cm.k[0], rr));
+    d = __fadd_rn(d, __fmul_rn(__fmul_rn(cm.k[1], rr), rr));
+    d = __fadd_rn(d, __fmul_rn(__fmul_rn(__fmul_rn(cm.k[2], rr), rr), rr));
+    const float t0 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[0]), y0n), y1n),
+                               __fmul_rn(cm.p[1], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y0n), y0n))));
+    const float t1 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[1]), y0n), y1n),
+                               __fmul_rn(cm.p[0], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y1n), y1n))));
+    y0n = __fdiv_rn(__fsub_rn(u0, t0), d);
+    y1n = __fdiv_rn(__fsub_rn(u1, t1), d);
+  }
+  const float g0 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[0], y0n), __fmul_rn(cm.R[3], y1n)), cm.R[6]);
+  const float g1 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[1], y0n), __fmul_rn(cm.R[4], y1n)), cm.R[7]);
+  const float g2 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[2], y0n), __fmul_rn(cm.R[5], y1n)), cm.R[8]);
+  const float len = sqrtf(dot3(g0, g1, g2, g0, g1, g2));
+  ray = make_float4(__fdiv_rn(g0, len), __fdiv_rn(g1, len), __fdiv_rn(g2, len), clampf(best, 0.0f, 1.0f));
+  return FVP_TRI_USED;
+}
+
+// step 8 over the views of `mask`, ascending: false iff degenerate
+__device__ __forceinline__ bool tri_solve(const float4* ray_s, const Cam* cam_s, int V, int J, int j, unsigned mask,
+                                          double min_det, float& X0, float& X1, float& X2) {
+  double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+  for (int u = 0; u < V; ++u) {
+    if (!((mask >> u) & 1u)) continue;
+    const float4 q = ray_s[u * J + j];
+    const double dx = q.x, dy = q.y, dz = q.z, w = q.w;
+    const double c0 = cam_s[u].T[0], c1 = cam_s[u].T[1], c2 = cam_s[u].T[2];
+    const double m00 = 1.0 - dx * dx, m11 = 1.0 - dy * dy, m22 = 1.0 - dz * dz;
+    const double m01 = -(dx * dy), m02 = -(dx * dz), m12 = -(dy * dz);
+    a00 = a00 + w * m00;
+    a01 = a01 + w * m01;
+    a02 = a02 + w * m02;
+    a11 = a11 + w * m11;
+    a12 = a12 + w * m12;
+    a22 = a22 + w * m22;
+    b0 = b0 + w * ((m00 * c0 + m01 * c1) + m02 * c2);
+    b1 = b1 + w * ((m01 * c0 + m11 * c1) + m12 * c2);
+    b2 = b2 + w * ((m02 * c0 + m12 * c1) + m22 * c2);
+  }
+  const double k00 = a11 * a22 - a12 * a12, k01 = a02 * a12 - a01 * a22, k02 = a01 * a12 - a02 * a11;
+  const double k11 = a00 * a22 - a02 * a02, k12 = a01 * a02 - a00 * a12, k22 = a00 * a11 - a01 * a01;
+  const double det = (a00 * k00 + a01 * k01) + a02 * k02;
+  const double t3 = ((a00 + a11) + a22) / 3.0;
+  if (!(det > min_det * ((t3 * t3) * t3))) return false;          // a NaN fails
+  X0 = float(((k00 * b0 + k01 * b1) + k02 * b2) / det);
+  X1 = float(((k01 * b0 + k11 * b1) + k12 * b2) / det);
+  X2 = float(((k02 * b0 + k12 * b1) + k22 * b2) / det);
+  return true;
+}
+
+// step 9 over the views of `mask`: e_v into the observation's fourth element
+__device__ __forceinline__ void tri_residuals(float4* ob_s, const Cam* cam_s, int V, int J, int j, unsigned mask, float X0,
+                                              float X1, float X2) {
+  for (int u = 0; u < V; ++u) {
+    if (!((mask >> u) & 1u)) continue;
+    float px, py, depth;
+    project_pixel(cam_s[u], X0, X1, X2, px, py, depth);
+    const float ex = __fsub_rn(px, ob_s[u * J + j].x), ey = __fsub_rn(py, ob_s[u * J + j].y);
+    ob_s[u * J + j].w = sqrtf(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)));
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_triangulate_joints(const float* __restrict__ heat_cl, const Cam* __restrict__ cams, const int* __restrict__ frame_set,
+                     const float* __restrict__ fused, const int* __restrict__ ids, const int* __restrict__ occluder, int N,
+                     FvpGeom g, TriParams tp, float* __restrict__ tri_poses, int* __restrict__ tri_count,
+                     float* __restrict__ tri_stats, float* __restrict__ obs, int* __restrict__ view_state) {
+  __shared__ Cam cam_s[FVP_MAX_VIEWS];
+  __shared__ float4 ray_s[256];
+  __shared__ float4 ob_s[256];
+  __shared__ int st_s[256];
+  const int V = g.V, J = g.J;
+  const int b = blockIdx.x / N, n = blockIdx.x - b * N;
+  const int tid = threadIdx.x;
+  const int set = frame_set[b];
+  const float* person = fused + (size_t(b) * N + n) * J * 5;
+  // uniform over the workgroup; a camera set outside the table is never read
+  const bool evaluated = set >= 0 && set < tp.nsets && person[3] >= 0.0f && (!ids || ids[b * N + n] >= 0);
+  if (evaluated && tid < V * FVP_CAM_FLOATS)
+    reinterpret_cast<float*>(cam_s)[tid] = reinterpret_cast<const float*>(cams + size_t(set) * V)[tid];
+  __syncthreads();
+  const int v = tid / J, j = tid - v * J;
+  const size_t o = ((size_t(b) * V + v) * N + n) * J + j;
+  if (v < V) {
+    int state = FVP_TRI_NOT_EVALUATED;
+    float4 ray = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ob = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    if (evaluated) {
+      const float* cl = heat_cl + (size_t(b) * V + v) * g.H * g.W * g.JP + j;
+      state = tri_observe(cl, cam_s[v], g, tp, person[j * 5 + 0], person[j * 5 + 1], person[j * 5 + 2], ray, ob);
+      if (state == FVP_TRI_USED && occluder && occluder[o] != -1) state = FVP_TRI_OCCLUDED;
+    }
+    ray_s[tid] = ray;
+    ob_s[tid] = ob;
+    st_s[tid] = state;
+  }
+  __syncthreads();
+  if (tid < J) {
+    const float P0 = person[tid * 5 + 0], P1 = person[tid * 5 + 1], P2 = person[tid * 5 + 2];
+    float X0 = P0, X1 = P1, X2 = P2, shift = 0.0f, rms = 0.0f;
+    int count = -2;
+    if (evaluated) {
+      unsigned mask = 0;
+      int usable = 0;
+      for (int u = 0; u < V; ++u)
+        if (st_s[u * J + tid] == FVP_TRI_USED) {
+          mask |= 1u << u;
+          ++usable;
+        }
+      count = usable;
+      float Y0 = 0.0f, Y1 = 0.0f, Y2 = 0.0f;
+      if (usable >= tp.min_views) {
+        if (!tri_solve(ray_s, cam_s, V, J, tid, mask, tp.min_det, Y0, Y1, Y2)) {
+          count = -1;
+        } else {
+          tri_residuals(ob_s, cam_s, V, J, tid, mask, Y0, Y1, Y2);
+          if (tp.reject_px > 0.0f) {
+            unsigned keep = 0;
+            int kept = 0;
+            for (int u = 0; u < V; ++u)
+              if (((mask >> u) & 1u) && !(ob_s[u * J + tid].w > tp.reject_px)) {
+                keep |= 1u << u;
+                ++kept;
+              }
+            float Z0, Z1, Z2;
+            if (keep != mask && kept >= tp.min_views && tri_solve(ray_s, cam_s, V, J, tid, keep, tp.min_det, Z0, Z1, Z2)) {
+              for (int u = 0; u < V; ++u)
+                if (((mask & ~keep) >> u) & 1u) {
+                  st_s[u * J + tid] = FVP_TRI_REJECTED;
+                  ob_s[u * J + tid].w = -1.0f;
+                }
+              mask = keep;
+              count = kept;
+              Y0 = Z0, Y1 = Z1, Y2 = Z2;
+              tri_residuals(ob_s, cam_s, V, J, tid, mask, Y0, Y1, Y2);
+            }
+          }
+          X0 = Y0, X1 = Y1, X2 = Y2;
+          const float s0 = __fsub_rn(X0, P0), s1 = __fsub_rn(X1, P1), s2 = __fsub_rn(X2, P2);
+          shift = sqrtf(dot3(s0, s1, s2, s0, s1, s2));
+          float num = 0.0f, den = 0.0f;
+          for (int u = 0; u < V; ++u) {
+            if (!((mask >> u) & 1u)) continue;
+            const float e = ob_s[u * J + tid].w, w = ray_s[u * J + tid].w;
+            num = __fadd_rn(num, __fmul_rn(w, __fmul_rn(e, e)));
+            den = __fadd_rn(den, w);
+          }
+          rms = sqrtf(__fdiv_rn(num, den));
+        }
+      }
+      if (count < tp.min_views)                       // too few views or degenerate: the usable views solved nothing
+        for (int u = 0; u < V; ++u)
+          if ((mask >> u) & 1u) st_s[u * J + tid] = FVP_TRI_UNSOLVED;
+    }
+    const size_t q = (size_t(b) * N + n) * J + tid;
+    if (tri_poses) {
+      tri_poses[q * 5 + 0] = X0;
+      tri_poses[q * 5 + 1] = X1;
+      tri_poses[q * 5 + 2] = X2;
+      tri_poses[q * 5 + 3] = person[tid * 5 + 3];
+      tri_poses[q * 5 + 4] = person[tid * 5 + 4];
+    }
+    if (tri_count) tri_count[q] = count;
+    if (tri_stats) {
+      tri_stats[q * 2 + 0] = shift;
+      tri_stats[q * 2 + 1] = rms;
+    }
+  }
+  __syncthreads();
+  if (v < V) {
+    if (obs) reinterpret_cast<float4*>(obs)[o] = ob_s[tid];
+    if (view_state) view_state[o] = st_s[tid];
+  }
+}
+
+// The residual per camera: one workgroup per (frame, view) over the N*J joint-views of obs / view_state.  Thread t sums the
+// used entries t, t + 256, ... in ascending order, then a tree of fixed shape (stride 128, 64, ..., 1) folds the 256
+// partial sums: the value does not depend on scheduling.
+__global__ void __launch_bounds__(256)
+k_view_residual(const float* __restrict__ obs, const int* __restrict__ view_state, int NJ, float* __restrict__ cam_resid,
+                int* __restrict__ cam_count) {
+  __shared__ float sum_s[256];
+  __shared__ int cnt_s[256];
+  const int tid = threadIdx.x;
+  const float4* ob = reinterpret_cast<const float4*>(obs) + size_t(blockIdx.x) * NJ;
+  const int* st = view_state + size_t(blockIdx.x) * NJ;
+  float sum = 0.0f;
+  int cnt = 0;
+  for (int q = tid; q < NJ; q += 256)
+    if (st[q] == FVP_TRI_USED) {
+      sum = __fadd_rn(sum, ob[q].w);
+      ++cnt;
+    }
+  sum_s[tid] = sum;
+  cnt_s[tid] = cnt;
+  __syncthreads();
+  for (int stride = 128; stride >= 1; stride >>= 1) {
+    if (tid < stride) {
+      sum_s[tid] = __fadd_rn(sum_s[tid], sum_s[tid + stride]);
+      cnt_s[tid] += cnt_s[tid + stride];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (cam_resid) cam_resid[blockIdx.x] = cnt_s[0] ? __fdiv_rn(sum_s[0], float(cnt_s[0])) : 0.0f;
+    if (cam_count) cam_count[blockIdx.x] = cnt_s[0];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Whole-space cubes (+ fused z-max).  A workgroup owns CPB = 256/Z complete z-columns so the
 // z-max never leaves the workgroup: values go through LDS [JP][256] and CPB*J threads each
 // reduce one column of one joint.
@@ -909,6 +1191,50 @@ extern "C" int fvp_joint_visibility(const float* fused_poses, const float* cams,
   hipLaunchKernelGGL(k_joint_visibility, dim3(B * N), dim3(256), 0, as_stream(s), fused_poses,
                      reinterpret_cast<const Cam*>(cams), frame_set, ids, views, V, N, J, prm, guard_mm, float(Ws - 1),
                      float(Hs - 1), occluder, vis_conf, vis_count);
+  return launch_status();
+}
+
+extern "C" int fvp_triangulate_joints(const float* heat_cl, const float* cams, int nsets, const int32_t* frame_set,
+                                      const float* fused_poses, const int32_t* ids, const int32_t* occluder, int B, int N,
+                                      const FvpGeom* g, int radius, float min_peak, int undistort_iters, int min_views,
+                                      float min_det, float reject_px, float* tri_poses, int32_t* tri_count,
+                                      float* tri_stats, float* obs, int32_t* view_state, float* cam_resid,
+                                      int32_t* cam_count, fvp_stream_t s) {
+  FVP_REQUIRE(heat_cl && cams && frame_set && fused_poses);
+  FVP_REQUIRE(tri_poses || tri_count || tri_stats || obs || view_state || cam_resid || cam_count);
+  FVP_REQUIRE((obs && view_state) || (!cam_resid && !cam_count));
+  FVP_REQUIRE(B >= 0 && N >= 1 && nsets >= 1 && radius >= 1 && min_views >= 2 && undistort_iters >= 0);
+  FVP_REQUIRE(fabsf(min_peak) <= FLT_MAX && fabsf(min_det) <= FLT_MAX && fabsf(reject_px) <= FLT_MAX);   // a NaN fails
+  if (int e = check_geom(g)) return e;
+  FVP_LIMIT(radius <= FVP_TRI_MAX_RADIUS && undistort_iters <= 16);
+  // heat-map cell -> pixel of the original image: the inverse of rt and of the heat scale, in double, rounded once
+  const double r0 = g->rt[0], r1 = g->rt[1], r2 = g->rt[2], r3 = g->rt[3], r4 = g->rt[4], r5 = g->rt[5];
+  const double sx = double(g->img_w) / double(g->hm_w), sy = double(g->img_h) / double(g->hm_h);
+  const double det = r0 * r4 - r1 * r3;
+  TriParams tp;
+  tp.inv[0] = float(r4 / det * sx);
+  tp.inv[1] = float(-r1 / det * sy);
+  tp.inv[2] = float((r1 * r5 - r4 * r2) / det);
+  tp.inv[3] = float(-r3 / det * sx);
+  tp.inv[4] = float(r0 / det * sy);
+  tp.inv[5] = float((r3 * r2 - r0 * r5) / det);
+  for (int i = 0; i < 6; ++i) FVP_REQUIRE(fabsf(tp.inv[i]) <= FLT_MAX);      // a singular rt, a zero heat-map size
+  tp.radius = radius;
+  tp.iters = undistort_iters;
+  tp.min_views = min_views;
+  tp.nsets = nsets;
+  tp.min_peak = min_peak;
+  tp.reject_px = reject_px;
+  tp.min_det = double(min_det);
+  if (B == 0) return 0;
+  const bool per_camera = cam_resid || cam_count;
+  ProfScope ps(FVP_K_OTHER, as_stream(s), 0.0, per_camera ? 2 : 1);
+  hipLaunchKernelGGL(k_triangulate_joints, dim3(B * N), dim3(256), 0, as_stream(s), heat_cl,
+                     reinterpret_cast<const Cam*>(cams), frame_set, fused_poses, ids, occluder, N, *g, tp, tri_poses,
+                     tri_count, tri_stats, obs, view_state);
+  if (per_camera)
+    hipLaunchKernelGGL(k_view_residual, dim3(B * g->V), dim3(256), 0, as_stream(s), obs, view_state, N * g->J, cam_resid,
+                       cam_count);
   return launch_status();
 }
 

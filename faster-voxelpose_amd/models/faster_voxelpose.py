@@ -22,6 +22,10 @@ a normalised, fixed-size image patch of every person in every view, cut out befo
 ``model.visibility = JointVisibility(cfg)`` (utils/visibility.py; needs ``evidence``) makes it also leave
 ``model.last_visibility = (occluder [B,V,N,J], vis_conf [B,N,J], vis_count [B,N,J])`` - which cameras see each joint past the
 other people's bodies, and the joint's confidence over those views only; one more launch behind the evidence's.
+``model.triangulator = JointTriangulator(cfg)`` (utils/triangulate.py) makes it also leave ``model.last_triangulation =
+(tri_poses [B,N,J,5], tri_count [B,N,J], tri_stats [B,N,J,2], obs [B,V,N,J,4], view_state [B,V,N,J], cam_resid [B,V], cam_count
+[B,V])`` - every joint triangulated from the heat-map peaks of the views, its distance from the fused joint, the reprojection
+residual per view and per camera; one or two more launches behind the evidence's and the visibility's.
 """
 import time
 
@@ -86,6 +90,14 @@ class FasterVoxelPoseNet(nn.Module):
         # the returned tuple is the same either way.  None: no launch more than without it.
         self.visibility = None
         self.last_visibility = None
+        # a utils.triangulate.JointTriangulator: forward() also triangulates every fused joint from the heat-map peaks of the
+        # views, behind the evidence and visibility launches, on the staging copy of this forward and the engine's camera
+        # tables - with `last_visibility[0]` as the occluder table when `visibility` is set - and keeps (tri_poses, tri_count,
+        # tri_stats, obs, view_state, cam_resid, cam_count) in `last_triangulation`.  The poses handed to tracker, smoother,
+        # overlay and crops stay the fused ones (feeding tri_poses onward is not built); the returned tuple is the same either
+        # way.  None: no launch more than without it.
+        self.triangulator = None
+        self.last_triangulation = None
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -198,6 +210,14 @@ class FasterVoxelPoseNet(nn.Module):
                                        frame_size=vis.frame_size or (hs, ws))
             if vis.feeds_conf:
                 conf = self.last_visibility[1]
+        if self.triangulator is not None:
+            # static-shape and sync-free: the parameters travel by value, the outputs are the triangulator's own tensors
+            g = self.engine.geom(resize_transform)
+            g.V = input_heatmaps.shape[1]
+            fs = self.engine.frame_sets(meta, cameras, g.V)
+            hcl = self.engine.heat_cl(input_heatmaps, g, reuse=True)
+            occ = self.last_visibility[0] if self.visibility is not None else None
+            self.last_triangulation = self.triangulator(fused_poses, self.engine.geo.cams, fs, hcl, occluder=occ, geom=g)
         if self.tracker is not None:
             # the frames' sequence rows are the engine's own table (frame_sets: cached, no upload here); static-shape and
             # sync-free, so a captured graph holds the launch and the state in device memory carries from replay to replay
@@ -289,7 +309,8 @@ class PipelinedForward:
     (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated).  A ``model.overlay`` is
     refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
     ``model.joint_evidence``.  So is a ``model.crops``: ``crops(frames, views, ids)`` on the consumer stream, before any
-    ``overlay.draw``.  And a ``model.visibility``: ``visibility(outputs[0], cameras, meta, views=views)`` there."""
+    ``overlay.draw``.  And a ``model.visibility``: ``visibility(outputs[0], cameras, meta, views=views)`` there.  And a
+    ``model.triangulator``: ``triangulator(outputs[0], cameras, meta, heat_cl)`` there."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -320,6 +341,10 @@ class PipelinedForward:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.visibility = None "
                                 "and call visibility(outputs[0], cameras, meta, views=views) on the consumer stream, with "
                                 "views from model.joint_evidence(outputs[0], ...)[0]")
+        if model.triangulator is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.triangulator = None "
+                                "and call triangulator(outputs[0], cameras, meta, heat_cl) on the consumer stream, with "
+                                "heat_cl from model.engine.heat_cl(outputs[3], geom)")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 17
+#define FVP_ABI_VERSION 18
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -34,6 +34,16 @@ extern "C" {
 #define FVP_TRACK_MAX_TRACKS 64 /* fvp_track_update: track slots per sequence (T) */
 #define FVP_VIS_MAX_PEOPLE 32   /* fvp_joint_visibility: person slots per frame (N) */
 #define FVP_VIS_MAX_PRIMS 64    /* fvp_joint_visibility: body primitives per person (L) */
+#define FVP_TRI_MAX_RADIUS 8    /* fvp_triangulate_joints: window half-size in heat-map cells */
+/* fvp_triangulate_joints: view_state */
+#define FVP_TRI_USED 1           /* the view is part of the joint's final solve */
+#define FVP_TRI_NOT_EVALUATED 0  /* absent person, or a frame_set entry outside the camera table */
+#define FVP_TRI_OUTSIDE (-1)     /* the joint is not finite, behind the camera, or its window holds no cell of the map */
+#define FVP_TRI_PEAK_LOW (-2)    /* the window's maximum is below min_peak (or every candidate is a NaN) */
+#define FVP_TRI_NOT_ENCLOSED (-3) /* the maximum lies on the window's border: the true peak may be outside */
+#define FVP_TRI_OCCLUDED (-4)    /* a peak was taken, but occluder says the view does not see the joint */
+#define FVP_TRI_REJECTED (-5)    /* dropped by the rejection round */
+#define FVP_TRI_UNSOLVED (-6)    /* usable, but the joint was not triangulated: too few usable views, or degenerate */
 
 #define FVP_EINVAL 10001 /* bad argument (null pointer, unsupported size) */
 #define FVP_ELIMIT 10002 /* size beyond a compiled limit (see message) */
@@ -651,6 +661,107 @@ int fvp_joint_visibility(const float* fused_poses /* [B][N][J][5] */, const floa
                          float guard_mm, int Hs, int Ws,
                          int32_t* occluder /* [B][V][N][J] */, float* vis_conf /* [B][N][J] */,
                          int32_t* vis_count /* [B][N][J] */, fvp_stream_t s);
+
+/* ---- triangulated joints from the views (ABI 18): a geometric second opinion per joint -------------------------------------
+ * Everything behind fvp_fuse_poses takes the voxel network's 3-D joints as given.  This call answers, for every fused joint,
+ * where the rays through the 2-D heat-map peaks of the usable views meet (independent of the fine grid's resolution, the
+ * soft-argmax and WeightNet), how far each view's peak lies from the reprojection of that point (pixels of the original
+ * image) and what that residual is per camera and frame - a camera that has been bumped stands apart from the others.
+ *
+ * heat_cl [B][V][H][W][JP], cams [nsets][V][FVP_CAM_FLOATS], frame_set [B] and g as for fvp_joint_evidence (V, J, JP, W, H
+ * are g's); nsets is the number of camera sets in cams; fused_poses [B][N][J][5]; ids [B][N] int32 (fvp_track_update) or NULL;
+ * occluder [B][V][N][J] int32 of fvp_joint_visibility or NULL.
+ *
+ * fp32 unless stated, every operation rounded on its own (no contraction) except the fmaf chains written as fma(); IEEE
+ * division and square root;  dot(p,q) = (p0*q0 + p1*q1) + p2*q2;  clamp(x,lo,hi) = fminf(fmaxf(x,lo),hi);
+ * a value is FINITE iff fabsf(x) <= FLT_MAX.  Person n of frame b is PRESENT iff fused_poses[b][n][0][3] >= 0 and (ids is
+ * NULL or ids[b][n] >= 0).  Frame b is EVALUATED iff 0 <= frame_set[b] < nsets (the camera table is not read otherwise);
+ * joint (b,n,j) is EVALUATED iff its frame is and its person is present.  Joints that are not evaluated: tri_count = -2,
+ * view_state = 0, tri_poses = fused_poses, tri_stats = 0, obs = (0,0,0,-1).
+ * On the host, once per call, in double from the fp32 fields of g, each result rounded to fp32 once (inv, passed by value):
+ *     det = rt0*rt4 - rt1*rt3,  sx = img_w / hm_w,  sy = img_h / hm_h,
+ *     inv0 = rt4/det*sx   inv1 = -rt1/det*sy   inv2 = (rt1*rt5 - rt4*rt2)/det
+ *     inv3 = -rt3/det*sx  inv4 = rt0/det*sy    inv5 = (rt3*rt2 - rt0*rt5)/det            (left to right)
+ * For an evaluated joint, P = fused_poses[b][n][j][0:3], and view v with camera record cm = cams[frame_set[b]][v]
+ * (R row-major, T, f, c, k, p), r = radius:
+ *   1. Window centre.  If P is not finite: state OUTSIDE.  (px, py, depth) = the camera model of fvp_joint_evidence
+ *      (project_pixel, csrc/fvp_geom.h: d = P - T, xc = R d as fma chains, y = xc.xy / (xc.z + 1e-5f), the radial and
+ *      tangential polynomial, px = f*u + c); depth = xc.z.  If not depth > 0: OUTSIDE.
+ *        ax = fma(rt2, 1, fma(rt1, py, rt0*px)),  ay = fma(rt5, 1, fma(rt4, py, rt3*px)),
+ *        hx = (ax*hm_w)/img_w,  hy = (ay*hm_h)/img_h                        (the heat-map cell coordinate, no clamp)
+ *      If hx or hy is not finite: OUTSIDE.  cxf = floorf(hx + 0.5f), cyf likewise.  If not (-r <= cxf <= W-1+r and
+ *      -r <= cyf <= H-1+r), compared as floats: OUTSIDE - the window holds no cell of the map.  Only then cx = int(cxf),
+ *      cy = int(cyf).  A view that is OUTSIDE costs no load from heat_cl.
+ *   2. Peak.  Candidates: the cells (x, y), |x-cx| <= r, |y-cy| <= r, 0 <= x < W, 0 <= y < H, of channel j, walked in
+ *      ascending (y, x).  A NaN is no candidate; a candidate replaces the winner iff it is strictly larger: a tie stays with
+ *      the smallest (y, x).  No candidate: PEAK_LOW, peak = 0.  Otherwise peak = the winner's value; if not peak >=
+ *      min_peak: PEAK_LOW; else if x == cx-r or x == cx+r or y == cy-r or y == cy+r (the border of the unclipped window):
+ *      NOT_ENCLOSED.
+ *   3. Sub-cell refinement, per axis with the neighbours m (at -1), c = peak, p (at +1) along that axis, a neighbour
+ *      outside the map being 0:  den = (2*c - m) - p,  delta = den > 0 ? clamp((0.5*(p - m))/den, -0.5, 0.5) : 0.
+ *      qx = float(x) + delta_x,  qy = float(y) + delta_y.
+ *   4. Back to the original image:  ox = fma(inv2, 1, fma(inv1, qy, inv0*qx)),  oy = fma(inv5, 1, fma(inv4, qy, inv3*qx)).
+ *   5. Undistort.  u0 = (ox - c0)/f0, u1 = (oy - c1)/f1, y = u; then undistort_iters rounds, both components from the old y:
+ *        rr = y0*y0 + y1*y1,  d = ((1 + k0*rr) + (k1*rr)*rr) + ((k2*rr)*rr)*rr,
+ *        t0 = ((2*p0)*y0)*y1 + p1*(rr + (2*y0)*y0),  t1 = ((2*p1)*y0)*y1 + p0*(rr + (2*y1)*y1),
+ *        y0 = (u0 - t0)/d,  y1 = (u1 - t1)/d.
+ *      The fixed point reached from y = u is the small-radius root of the polynomial, the physical one where it folds.
+ *   6. Ray.  g_k = (R[k]*y0 + R[3+k]*y1) + R[6+k], k = 0..2 (R transposed times (y0, y1, 1));  d = g / sqrtf(dot(g,g));
+ *      origin C = T;  w = clamp(peak, 0, 1).  The view's state is USED - or OCCLUDED, if occluder is given and
+ *      occluder[b][v][n][j] != -1.
+ *   7. The usable views are those in state USED.  Fewer than min_views: tri_count = their number, not triangulated.  The
+ *      usable views of a joint that is not triangulated (here or in step 8) end in state UNSOLVED.
+ *   8. Solve, in fp64 (every fp32 input converted exactly, every operation rounded on its own), over the usable views in
+ *      ascending v, all sums from 0:
+ *        m00 = 1 - dx*dx, m11 = 1 - dy*dy, m22 = 1 - dz*dz, m01 = -(dx*dy), m02 = -(dx*dz), m12 = -(dy*dz)
+ *        Aik = Aik + w*mik (six sums),  b0 = b0 + w*((m00*C0 + m01*C1) + m02*C2), b1 and b2 with rows (m01, m11, m12),
+ *        (m02, m12, m22).
+ *        k00 = A11*A22 - A12*A12   k01 = A02*A12 - A01*A22   k02 = A01*A12 - A02*A11
+ *        k11 = A00*A22 - A02*A02   k12 = A01*A02 - A00*A12   k22 = A00*A11 - A01*A01
+ *        det = (A00*k00 + A01*k01) + A02*k02,  t3 = ((A00 + A11) + A22)/3
+ *      DEGENERATE iff not det > double(min_det)*((t3*t3)*t3) (a NaN fails): tri_count = -1, not triangulated.  Otherwise
+ *        X0 = ((k00*b0 + k01*b1) + k02*b2)/det, X1 = ((k01*b0 + k11*b1) + k12*b2)/det, X2 = ((k02*b0 + k12*b1) + k22*b2)/det,
+ *      each rounded to fp32 once.
+ *   9. Residual of every view of the solve:  (qx, qy, .) = the camera model at X;  ex = qx - ox, ey = qy - oy,
+ *      e_v = sqrtf(ex*ex + ey*ey).
+ *  10. One rejection round, iff reject_px > 0: keep = the views of the solve with not e_v > reject_px.  Iff keep differs from
+ *      the solve's views, holds at least min_views views and step 8 over keep is not degenerate, its X replaces the first,
+ *      the dropped views get state REJECTED and e_v = -1, and step 9 is repeated over keep.  Otherwise the first solution,
+ *      its residuals and states stand.  The round is not iterated.
+ * Outputs; every element of a non-NULL output is written by every call; any may be NULL, not all of them; cam_resid and
+ * cam_count are reduced from obs and view_state and need both:
+ *     tri_poses  [B][N][J][5]    xyz = X where triangulated, else P; elements 3 and 4 copied from fused_poses: the tensor
+ *                                drops in wherever fused_poses goes (tracker, smoother, overlay, evidence);
+ *     tri_count  [B][N][J] int32 the views of the final solve (>= min_views); 0..min_views-1: that many usable views, not
+ *                                triangulated; -1 degenerate; -2 not evaluated;
+ *     tri_stats  [B][N][J][2]    shift_mm = sqrtf(dot(X - P, X - P)),  rms_px = sqrtf(num/den) with num = num + w*(e_v*e_v),
+ *                                den = den + w over the views of the final solve in ascending v; (0, 0) when not triangulated;
+ *     obs        [B][V][N][J][4] (ox, oy, peak, e_v); e_v = -1 unless the state is USED; ox = oy = 0 in the states
+ *                                NOT_EVALUATED, OUTSIDE, PEAK_LOW and NOT_ENCLOSED, peak = 0 in the first two (and where
+ *                                every candidate is a NaN);
+ *     view_state [B][V][N][J] int32  FVP_TRI_USED ... FVP_TRI_UNSOLVED above;
+ *     cam_resid  [B][V] fp32, cam_count [B][V] int32: the mean e_v and the number of USED joint-views of view v in frame b.
+ *                                With q = n*J + j: thread t of 256 adds the used entries q = t, t+256, ... in ascending
+ *                                order from 0, then the 256 partial sums fold as s[t] = s[t] + s[t+h] for h = 128, 64, ..., 1;
+ *                                cam_resid = s[0]/float(count), 0 when the count is 0.  No dependence on scheduling.
+ * FVP_EINVAL: a null heat_cl, cams, frame_set, fused_poses or g; all outputs null; cam_resid or cam_count without obs and
+ * view_state; B < 0; N or nsets < 1; radius < 1; min_views < 2; undistort_iters < 0; min_peak, min_det or reject_px not finite;
+ * g's JP, W or H invalid; an rt that cannot be inverted.  FVP_ELIMIT: J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS, radius >
+ * FVP_TRI_MAX_RADIUS, undistort_iters > 16.  Nothing is written when an error is returned.  B == 0 returns 0 without a launch.
+ * One launch (two with cam_resid / cam_count), no host synchronisation, no atomics: one workgroup per (b, n), the camera
+ * records in LDS, one thread per (v, j) for steps 1-6, one thread per j for steps 7-10.
+ * Suggested parameters - guesses, not tuned on real data: radius 3, min_peak 0.3, undistort_iters 8, min_views 2,
+ * min_det 1e-3, reject_px 0 (off).  Not built: bundle adjustment or re-calibration, an iterated rejection, triangulated
+ * poses fed into tracker or smoother by default. */
+int fvp_triangulate_joints(const float* heat_cl /* [B][V][H][W][JP] */, const float* cams /* [nsets][V][FVP_CAM_FLOATS] */,
+                           int nsets, const int32_t* frame_set /* [B] */, const float* fused_poses /* [B][N][J][5] */,
+                           const int32_t* ids /* [B][N] or NULL */, const int32_t* occluder /* [B][V][N][J] or NULL */,
+                           int B, int N, const FvpGeom* g,
+                           int radius, float min_peak, int undistort_iters, int min_views, float min_det, float reject_px,
+                           float* tri_poses /* [B][N][J][5] */, int32_t* tri_count /* [B][N][J] */,
+                           float* tri_stats /* [B][N][J][2] */, float* obs /* [B][V][N][J][4] */,
+                           int32_t* view_state /* [B][V][N][J] */, float* cam_resid /* [B][V] */,
+                           int32_t* cam_count /* [B][V] */, fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

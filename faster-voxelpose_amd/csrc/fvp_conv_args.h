@@ -70,6 +70,8 @@ struct ConvArgs {
   int nflags;         // Winograd: entries of plane_valid staged in LDS (0: every unit is valid)
   unsigned m_vd;      // Winograd: fdiv magic of valid_div
   int epi_off;        // k_conv_dma: float offset of the BN vectors' copy in dynamic LDS (behind slots and epilogue scratch)
+  int shcols;         // Winograd: 0 = every lane transforms its whole 4x4 patch; 1 / 2 = the tiles of a row share the first
+                      // pass of the input transform, the neighbouring tile sits 1 (W = 32) / 2 (W = 16) lanes away
 };
 
 
@@ -88,6 +90,22 @@ __device__ __forceinline__ KArgsPtr fresh_args_ptr() {
 }
 #define FVP_FRESH_ARGS(a) fresh_args_ptr()
 #endif
+
+// The value of `x` in the lane SHIFT lanes to the left (LEFT) or right inside the lane's DPP row of 16; +0.0 where that lane
+// lies outside the row.  row_shr / row_shl with bound_ctrl and full masks: hipcc folds the move into the consuming
+// v_sub_f32 / v_subrev_f32 as its DPP source operand (no instruction of its own).
+template <int SHIFT, bool LEFT>
+__device__ __forceinline__ float dpp_row_neighbour(float x) {
+  static_assert(SHIFT >= 1 && SHIFT <= 15, "row shift");
+#if defined(HIPEMU)
+  const int lane = hipemu::cur->lane, src = LEFT ? lane - SHIFT : lane + SHIFT;
+  const bool inside = src >= 0 && (src >> 4) == (lane >> 4);
+  const float r = hipemu_shfl_from(x, inside ? src : lane);
+  return inside ? r : 0.0f;
+#else
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), (LEFT ? 0x110 : 0x100) + SHIFT, 0xf, 0xf, true));
+#endif
+}
 
 // The LDS-DMA of k_conv_dma / k_conv_wino addresses a work unit's input and weights with 32-bit BYTE offsets against a
 // raw buffer descriptor whose num_records is 0x7ffffff0: per-lane offset (up to (TN + 1) planes of the plane group) plus

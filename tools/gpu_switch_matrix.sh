@@ -24,3 +24,6 @@ run FVP_CONV_NO_K7=1
 run FVP_BB_NO_FUSE_STEM=1 FVP_BB_NO_FUSE_BLOCK=1
 run FVP_TRI_NO_Q5=1
 run FVP_WINO_GENERIC=1
+run FVP_WINO_SHARED_COLS=0
+run FVP_WINO_SHARED_COLS=1
+run FVP_WINO_SHARED_COLS=2

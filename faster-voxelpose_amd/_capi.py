@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 18           # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 19           # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -20,6 +20,8 @@ FVP_TRACK_MAX_TRACKS = 64
 FVP_VIS_MAX_PEOPLE = 32
 FVP_VIS_MAX_PRIMS = 64
 FVP_TRI_MAX_RADIUS = 8
+FVP_CAL_ACC = 32
+FVP_CAL_OK, FVP_CAL_CLAMPED, FVP_CAL_FEW, FVP_CAL_DEGENERATE = 1, 2, 0, -1
 
 OP_CONV, OP_POOL2, OP_CONVT2 = 0, 1, 2
 EPI_RELU, EPI_RES, EPI_RES_AFTER_RELU = 1, 2, 4
@@ -97,6 +99,8 @@ SIGNATURES = {
     "fvp_joint_visibility": [_P, _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(_F), _I, _F, _I, _I, _P, _P,
                              _P, _P],
     "fvp_triangulate_joints": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _G, _I, _F, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
+    "fvp_camera_refit_accumulate": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P],
+    "fvp_camera_refit_solve": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P],
     "fvp_bb_input": [_P, _P, _I, _I, _I, _I, _P],
     "fvp_bb_pack": [_P, _P, _P, _P, _P, _P, _F, C.POINTER(FvpBbOp), _P, _P, _P],
     "fvp_bb_run": [C.POINTER(FvpBbOp), _I, _P, _P, C.POINTER(_P), _I, _I, _P, _I, _P, _P],

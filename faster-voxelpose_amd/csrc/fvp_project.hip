@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <climits>
 #include <cstdlib>
 
 #include "fvp_common.h"
@@ -266,6 +267,25 @@ __device__ __forceinline__ float tri_refine(float m, float c, float p) {
   return den > 0.0f ? clampf(__fdiv_rn(__fmul_rn(0.5f, __fsub_rn(p, m)), den), -0.5f, 0.5f) : 0.0f;
 }
 
+// step 5: the observed pixel of the original image back through the lens model, `iters` fixed-point rounds from y = u
+// (shared with the camera re-fit below: one function, one set of bits)
+__device__ __forceinline__ void tri_undistort(const Cam& cm, float ox, float oy, int iters, float& y0n, float& y1n) {
+  const float u0 = __fdiv_rn(__fsub_rn(ox, cm.c[0]), cm.f[0]), u1 = __fdiv_rn(__fsub_rn(oy, cm.c[1]), cm.f[1]);
+  y0n = u0, y1n = u1;
+  for (int it = 0; it < iters; ++it) {
+    const float rr = __fadd_rn(__fmul_rn(y0n, y0n), __fmul_rn(y1n, y1n));
+    float d = __fadd_rn(1.0f, __fmul_rn(cm.k[0], rr));
+    d = __fadd_rn(d, __fmul_rn(__fmul_rn(cm.k[1], rr), rr));
+    d = __fadd_rn(d, __fmul_rn(__fmul_rn(__fmul_rn(cm.k[2], rr), rr), rr));
+    const float t0 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[0]), y0n), y1n),
+                               __fmul_rn(cm.p[1], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y0n), y0n))));
+    const float t1 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[1]), y0n), y1n),
+                               __fmul_rn(cm.p[0], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y1n), y1n))));
+    y0n = __fdiv_rn(__fsub_rn(u0, t0), d);
+    y1n = __fdiv_rn(__fsub_rn(u1, t1), d);
+  }
+}
+
 // steps 1-6 for one (view, joint): the state, the ray (d, w) and the observation (ox, oy, peak, -1)
 __device__ __forceinline__ int tri_observe(const float* __restrict__ cl, const Cam& cm, const FvpGeom& g,
                                            const TriParams& tp, float wx, float wy, float wz, float4& ray, float4& ob) {
@@ -314,20 +334,8 @@ __device__ __forceinline__ int tri_observe(const float* __restrict__ cl, const C
   const float oy = __fmaf_rn(tp.inv[5], 1.0f, __fmaf_rn(tp.inv[4], qy, __fmul_rn(tp.inv[3], qx)));
   ob.x = ox;
   ob.y = oy;
-  const float u0 = __fdiv_rn(__fsub_rn(ox, cm.c[0]), cm.f[0]), u1 = __fdiv_rn(__fsub_rn(oy, cm.c[1]), cm.f[1]);
-  float y0n = u0, y1n = u1;
-  for (int it = 0; it < tp.iters; ++it) {
-    const float rr = __fadd_rn(__fmul_rn(y0n, y0n), __fmul_rn(y1n, y1n));
-    float d = __fadd_rn(1.0f, __fmul_rn(cm.k[0], rr));
-    d = __fadd_rn(d, __fmul_rn(__fmul_rn(cm.k[1], rr), rr));
-    d = __fadd_rn(d, __fmul_rn(__fmul_rn(__fmul_rn(cm.k[2], rr), rr), rr));
-    const float t0 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[0]), y0n), y1n),
-                               __fmul_rn(cm.p[1], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y0n), y0n))));
-    const float t1 = __fadd_rn(__fmul_rn(__fmul_rn(__fmul_rn(2.0f, cm.p[1]), y0n), y1n),
-                               __fmul_rn(cm.p[0], __fadd_rn(rr, __fmul_rn(__fmul_rn(2.0f, y1n), y1n))));
-    y0n = __fdiv_rn(__fsub_rn(u0, t0), d);
-    y1n = __fdiv_rn(__fsub_rn(u1, t1), d);
-  }
+  float y0n, y1n;
+  tri_undistort(cm, ox, oy, tp.iters, y0n, y1n);
   const float g0 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[0], y0n), __fmul_rn(cm.R[3], y1n)), cm.R[6]);
   const float g1 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[1], y0n), __fmul_rn(cm.R[4], y1n)), cm.R[7]);
   const float g2 = __fadd_rn(__fadd_rn(__fmul_rn(cm.R[2], y0n), __fmul_rn(cm.R[5], y1n)), cm.R[8]);
@@ -524,6 +532,220 @@ k_view_residual(const float* __restrict__ obs, const int* __restrict__ view_stat
     if (cam_resid) cam_resid[blockIdx.x] = cnt_s[0] ? __fdiv_rn(sum_s[0], float(cnt_s[0])) : 0.0f;
     if (cam_count) cam_count[blockIdx.x] = cnt_s[0];
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Camera re-fit (fvp_camera_refit_accumulate / fvp_camera_refit_solve, include/fvp.h): a robust resection of every camera
+// against the 3-D joints, one Gauss-Newton step on its six extrinsic parameters.  All of it in fp64, every operation
+// rounded on its own (this file is built without contraction); only the undistortion is the triangulation's fp32 function.
+//
+// Accumulate: one workgroup of 256 threads per camera (set, view).  Thread t walks the joint-views q = t, t + 256, ... of
+// the whole batch in ascending order and keeps the 31 sums of its counting entries in registers (every index below is a
+// compile-time constant after unrolling: nothing in scratch); the 256 partial vectors then fold through LDS in four slices
+// of eight elements, [element][thread] so that neighbouring lanes touch neighbouring doubles, as a tree of fixed shape
+// (stride 128, 64, ..., 1).  No atomics: the sums do not depend on scheduling.
+__host__ __device__ constexpr int refit_ut(int i, int k) { return i * 6 - i * (i - 1) / 2 + (k - i); }   // H_ik, i <= k
+__host__ __device__ constexpr int refit_lt(int i, int k) { return i * (i + 1) / 2 + k; }                 // L_ik, k <= i
+
+__global__ void __launch_bounds__(256)
+k_camera_refit_accumulate(const float* __restrict__ points, const float* __restrict__ obs,
+                          const int* __restrict__ view_state, const Cam* __restrict__ cams,
+                          const int* __restrict__ frame_set, int B, int V, int NJ, int iters, float huber_px, float decay,
+                          double* __restrict__ acc) {
+  __shared__ double red_s[8 * 256];
+  const int tid = threadIdx.x;
+  const int set = blockIdx.x / V, v = blockIdx.x - set * V;
+  const Cam cm = cams[blockIdx.x];
+  const double f0 = cm.f[0], f1 = cm.f[1], hub = huber_px;
+  double p[FVP_CAL_ACC];
+#pragma unroll
+  for (int i = 0; i < FVP_CAL_ACC; ++i) p[i] = 0.0;
+  const int total = B * NJ;
+  for (int q = tid; q < total; q += 256) {
+    const int b = q / NJ;
+    if (frame_set[b] != set) continue;
+    const size_t o = (size_t(b) * V + v) * NJ + (q - b * NJ);
+    if (view_state[o] != FVP_TRI_USED) continue;
+    const float X0 = points[size_t(q) * 5 + 0], X1 = points[size_t(q) * 5 + 1], X2 = points[size_t(q) * 5 + 2];
+    const float4 ob = reinterpret_cast<const float4*>(obs)[o];
+    if (!(fabsf(X0) <= FLT_MAX && fabsf(X1) <= FLT_MAX && fabsf(X2) <= FLT_MAX)) continue;
+    if (!(fabsf(ob.x) <= FLT_MAX && fabsf(ob.y) <= FLT_MAX)) continue;
+    const float wf = clampf(ob.z, 0.0f, 1.0f);
+    if (!(wf > 0.0f)) continue;
+    const double d0 = double(X0) - double(cm.T[0]), d1 = double(X1) - double(cm.T[1]), d2 = double(X2) - double(cm.T[2]);
+    const double xc0 = (double(cm.R[0]) * d0 + double(cm.R[1]) * d1) + double(cm.R[2]) * d2;
+    const double xc1 = (double(cm.R[3]) * d0 + double(cm.R[4]) * d1) + double(cm.R[5]) * d2;
+    const double z = (double(cm.R[6]) * d0 + double(cm.R[7]) * d1) + double(cm.R[8]) * d2;
+    if (!(z > 1.0)) continue;
+    float y0f, y1f;
+    tri_undistort(cm, ob.x, ob.y, iters, y0f, y1f);
+    const double iz = 1.0 / z, u = xc0 / z, w = xc1 / z;
+    const double r0 = (double(y0f) - u) * f0, r1 = (double(y1f) - w) * f1;
+    const double Ju[6] = {f0 * (-(u * w)), f0 * (1.0 + u * u), f0 * (-w), f0 * iz, 0.0, f0 * (-(u * iz))};
+    const double Jv[6] = {f1 * (-(1.0 + w * w)), f1 * (u * w), f1 * u, 0.0, f1 * iz, f1 * (-(w * iz))};
+    const double e2 = r0 * r0 + r1 * r1, e = sqrt(e2);
+    const double h = (hub > 0.0 && e > hub) ? hub / e : 1.0;
+    const double ww = double(wf) * h;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int k = i; k < 6; ++k) p[refit_ut(i, k)] = p[refit_ut(i, k)] + ww * ((Ju[i] * Ju[k]) + (Jv[i] * Jv[k]));
+      p[21 + i] = p[21 + i] + ww * ((Ju[i] * r0) + (Jv[i] * r1));
+    }
+    p[27] = p[27] + ww;
+    p[28] = p[28] + ww * e2;
+    p[29] = p[29] + 1.0;
+    p[30] = p[30] + (h < 1.0 ? 1.0 : 0.0);
+  }
+  double* out = acc + size_t(blockIdx.x) * FVP_CAL_ACC;
+#pragma unroll
+  for (int sl = 0; sl < FVP_CAL_ACC / 8; ++sl) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) red_s[i * 256 + tid] = p[sl * 8 + i];
+    __syncthreads();
+    for (int stride = 128; stride >= 1; stride >>= 1) {
+      if (tid < stride) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) red_s[i * 256 + tid] = red_s[i * 256 + tid] + red_s[i * 256 + tid + stride];
+      }
+      __syncthreads();
+    }
+    if (tid < 8) {
+      const int i = sl * 8 + tid;
+      out[i] = i == FVP_CAL_ACC - 1 ? 0.0 : out[i] * double(decay) + red_s[tid * 256];
+    }
+    __syncthreads();
+  }
+}
+
+// Solve: one thread per camera.  The 6x6 system lives in named registers: every loop below has compile-time bounds and is
+// unrolled, so that no array is indexed by a run-time value.  The Cholesky factor overwrites the scaled matrix in place.
+__global__ void __launch_bounds__(64)
+k_camera_refit_solve(const double* __restrict__ acc, const Cam* __restrict__ cams_in, int ncam, int min_obs, double lambda,
+                     double min_pivot, double max_angle, double max_shift, Cam* __restrict__ cams_out,
+                     float* __restrict__ cal_stats, int* __restrict__ cal_state) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= ncam) return;
+  const double* a = acc + size_t(c) * FVP_CAL_ACC;
+  Cam cm = cams_in[c];
+  double g[6], D[6], A[21], dl[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) g[i] = a[21 + i];
+  const double sw = a[27], se = a[28], count = a[29];
+  const double rms_before = sw > 0.0 ? sqrt(se / sw) : 0.0;
+  double theta = 0.0, sigma = 0.0, rms_pred = 0.0, minpiv = 0.0;
+  int state = FVP_CAL_OK;
+  if (!(count >= double(min_obs))) state = FVP_CAL_FEW;
+  if (state == FVP_CAL_OK) {
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const double hii = a[refit_ut(i, i)];
+      bad = bad || !(hii > 0.0);
+      D[i] = sqrt(hii);
+    }
+    if (bad) state = FVP_CAL_DEGENERATE;
+  }
+  if (state == FVP_CAL_OK) {
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int k = 0; k < i; ++k) A[refit_lt(i, k)] = a[refit_ut(k, i)] / (D[i] * D[k]);
+      A[refit_lt(i, i)] = a[refit_ut(i, i)] / (D[i] * D[i]) + lambda;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double piv = A[refit_lt(j, j)];
+#pragma unroll
+      for (int k = 0; k < j; ++k) piv = piv - A[refit_lt(j, k)] * A[refit_lt(j, k)];
+      bad = bad || !(piv > min_pivot);                       // a NaN fails
+      minpiv = (j == 0 || piv < minpiv) ? piv : minpiv;
+      const double ljj = sqrt(piv);
+      A[refit_lt(j, j)] = ljj;
+#pragma unroll
+      for (int i = j + 1; i < 6; ++i) {
+        double t = A[refit_lt(i, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) t = t - A[refit_lt(i, k)] * A[refit_lt(j, k)];
+        A[refit_lt(i, j)] = t / ljj;
+      }
+    }
+    if (bad) state = FVP_CAL_DEGENERATE;
+  }
+  if (state == FVP_CAL_OK) {
+    double y[6], zt[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double t = g[i] / D[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) t = t - A[refit_lt(i, k)] * y[k];
+      y[i] = t / A[refit_lt(i, i)];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+      double t = y[i];
+#pragma unroll
+      for (int k = i + 1; k < 6; ++k) t = t - A[refit_lt(k, i)] * zt[k];
+      zt[i] = t / A[refit_lt(i, i)];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) dl[i] = zt[i] / D[i];
+    theta = sqrt((dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2]);
+    sigma = sqrt((dl[3] * dl[3] + dl[4] * dl[4]) + dl[5] * dl[5]);
+    if (!(theta <= DBL_MAX && sigma <= DBL_MAX)) state = FVP_CAL_DEGENERATE;      // a step that is not finite is no step
+  }
+  if (state == FVP_CAL_OK) {
+    const double gd = ((((g[0] * dl[0] + g[1] * dl[1]) + g[2] * dl[2]) + g[3] * dl[3]) + g[4] * dl[4]) + g[5] * dl[5];
+    const double left = se - gd;
+    rms_pred = sw > 0.0 ? sqrt((left > 0.0 ? left : 0.0) / sw) : 0.0;
+    double kappa = 1.0;
+    if (theta > max_angle) kappa = max_angle / theta;
+    if (sigma > max_shift) {
+      const double k2 = max_shift / sigma;
+      if (k2 < kappa) kappa = k2;
+    }
+    if (kappa < 1.0) {
+      state = FVP_CAL_CLAMPED;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) dl[i] = dl[i] * kappa;
+      theta = sqrt((dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2]);
+      sigma = sqrt((dl[3] * dl[3] + dl[4] * dl[4]) + dl[5] * dl[5]);
+    }
+    // Cayley retraction: the unit quaternion (1, w/2) / |(1, w/2)| - no transcendental function anywhere
+    const double h0 = 0.5 * dl[0], h1 = 0.5 * dl[1], h2 = 0.5 * dl[2];
+    const double n = sqrt(1.0 + ((h0 * h0 + h1 * h1) + h2 * h2));
+    const double qw = 1.0 / n, qx = h0 / n, qy = h1 / n, qz = h2 / n;
+    const double C[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qz * qw), 2.0 * (qx * qz + qy * qw),
+                         2.0 * (qx * qy + qz * qw), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qx * qw),
+                         2.0 * (qx * qz - qy * qw), 2.0 * (qy * qz + qx * qw), 1.0 - 2.0 * (qx * qx + qy * qy)};
+    double Rn[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        Rn[3 * i + k] = (C[3 * i] * double(cm.R[k]) + C[3 * i + 1] * double(cm.R[3 + k])) + C[3 * i + 2] * double(cm.R[6 + k]);
+    double Tn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Tn[k] = double(cm.T[k]) - ((Rn[k] * dl[3] + Rn[3 + k] * dl[4]) + Rn[6 + k] * dl[5]);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cm.R[i] = float(Rn[i]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cm.T[k] = float(Tn[k]);
+  } else {
+    theta = sigma = rms_pred = minpiv = 0.0;
+  }
+  cams_out[c] = cm;
+  if (cal_stats) {
+    float* st = cal_stats + size_t(c) * 6;
+    st[0] = float(theta);
+    st[1] = float(sigma);
+    st[2] = float(rms_before);
+    st[3] = float(rms_pred);
+    st[4] = float(count);
+    st[5] = float(minpiv);
+  }
+  if (cal_state) cal_state[c] = state;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1235,6 +1457,37 @@ extern "C" int fvp_triangulate_joints(const float* heat_cl, const float* cams, i
   if (per_camera)
     hipLaunchKernelGGL(k_view_residual, dim3(B * g->V), dim3(256), 0, as_stream(s), obs, view_state, N * g->J, cam_resid,
                        cam_count);
+  return launch_status();
+}
+
+extern "C" int fvp_camera_refit_accumulate(const float* points, const float* obs, const int32_t* view_state,
+                                           const float* cams, int nsets, const int32_t* frame_set, int B, int V, int N, int J,
+                                           int undistort_iters, float huber_px, float decay, double* acc, fvp_stream_t s) {
+  FVP_REQUIRE(points && obs && view_state && cams && frame_set && acc);
+  FVP_REQUIRE(B >= 0 && V >= 1 && N >= 1 && J >= 1 && nsets >= 1 && undistort_iters >= 0);
+  FVP_REQUIRE(fabsf(huber_px) <= FLT_MAX && decay >= 0.0f && decay <= 1.0f);                             // a NaN fails
+  FVP_LIMIT(V <= FVP_MAX_VIEWS && J <= FVP_MAX_JOINTS && undistort_iters <= 16);
+  FVP_LIMIT(static_cast<long long>(B) * N * J <= INT_MAX && static_cast<long long>(nsets) * V <= INT_MAX);
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s), 0.0, 1);
+  hipLaunchKernelGGL(k_camera_refit_accumulate, dim3(nsets * V), dim3(256), 0, as_stream(s), points, obs, view_state,
+                     reinterpret_cast<const Cam*>(cams), frame_set, B, V, N * J, undistort_iters, huber_px, decay, acc);
+  return launch_status();
+}
+
+extern "C" int fvp_camera_refit_solve(const double* acc, const float* cams_in, int nsets, int V, int min_obs, float lambda,
+                                      float min_pivot, float max_angle_rad, float max_shift_mm, float* cams_out,
+                                      float* cal_stats, int32_t* cal_state, fvp_stream_t s) {
+  FVP_REQUIRE(acc && cams_in && cams_out && cams_out != cams_in);
+  FVP_REQUIRE(nsets >= 1 && V >= 1 && min_obs >= 6);
+  FVP_REQUIRE(lambda >= 0.0f && lambda <= FLT_MAX);                                                      // a NaN fails
+  FVP_REQUIRE(min_pivot > 0.0f && min_pivot <= FLT_MAX && max_angle_rad > 0.0f && max_angle_rad <= FLT_MAX);
+  FVP_REQUIRE(max_shift_mm > 0.0f && max_shift_mm <= FLT_MAX);
+  FVP_LIMIT(V <= FVP_MAX_VIEWS && static_cast<long long>(nsets) * V <= INT_MAX);
+  ProfScope ps(FVP_K_OTHER, as_stream(s), 0.0, 1);
+  hipLaunchKernelGGL(k_camera_refit_solve, dim3(ceil_div(nsets * V, 64)), dim3(64), 0, as_stream(s), acc,
+                     reinterpret_cast<const Cam*>(cams_in), nsets * V, min_obs, double(lambda), double(min_pivot),
+                     double(max_angle_rad), double(max_shift_mm), reinterpret_cast<Cam*>(cams_out), cal_stats, cal_state);
   return launch_status();
 }
 

@@ -26,6 +26,9 @@ other people's bodies, and the joint's confidence over those views only; one mor
 (tri_poses [B,N,J,5], tri_count [B,N,J], tri_stats [B,N,J,2], obs [B,V,N,J,4], view_state [B,V,N,J], cam_resid [B,V], cam_count
 [B,V])`` - every joint triangulated from the heat-map peaks of the views, its distance from the fused joint, the reprojection
 residual per view and per camera; one or two more launches behind the evidence's and the visibility's.
+``model.recalibrator = CameraRefiner(cfg)`` (utils/recalibrate.py; needs ``triangulator``) makes it also accumulate every
+forward's observations against the engine's camera tables in ``model.recalibrator.acc`` - one more launch behind the
+triangulation's; ``model.recalibrator.solve(model.engine.geo.cams)`` then gives the corrected camera records.
 """
 import time
 
@@ -98,6 +101,13 @@ class FasterVoxelPoseNet(nn.Module):
         # way.  None: no launch more than without it.
         self.triangulator = None
         self.last_triangulation = None
+        # a utils.recalibrate.CameraRefiner (needs `triangulator`): forward() also adds this batch's observations to the
+        # refiner's accumulators - one launch right behind the triangulation's, on `last_triangulation` and the engine's
+        # camera tables; `recalibrator_points`: "fused" (the forward's joints) or "tri" (the triangulated ones) as the 3-D
+        # points.  Solving and adopting stay with the caller (`recalibrator.solve(engine.geo.cams)`, `camera_dicts`): the
+        # engine's tables are never swapped here.  The returned tuple is the same either way.  None: no launch more.
+        self.recalibrator = None
+        self.recalibrator_points = "fused"
         self.eval()
 
     def joint_evidence(self, fused_poses, input_heatmaps, meta, cameras, resize_transform):
@@ -218,6 +228,16 @@ class FasterVoxelPoseNet(nn.Module):
             hcl = self.engine.heat_cl(input_heatmaps, g, reuse=True)
             occ = self.last_visibility[0] if self.visibility is not None else None
             self.last_triangulation = self.triangulator(fused_poses, self.engine.geo.cams, fs, hcl, occluder=occ, geom=g)
+        if self.recalibrator is not None:
+            if self.triangulator is None:
+                raise capi.FvpError("model.recalibrator reads the triangulation's obs and view_state: set model.triangulator "
+                                    "= JointTriangulator(cfg) as well")
+            if self.recalibrator_points not in ("fused", "tri"):
+                raise capi.FvpError(f"model.recalibrator_points must be 'fused' or 'tri', got {self.recalibrator_points!r}")
+            tri = self.last_triangulation
+            pts = fused_poses if self.recalibrator_points == "fused" else tri[0]
+            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
+            self.recalibrator.accumulate(pts, tri[3], tri[4], self.engine.geo.cams, fs)
         if self.tracker is not None:
             # the frames' sequence rows are the engine's own table (frame_sets: cached, no upload here); static-shape and
             # sync-free, so a captured graph holds the launch and the state in device memory carries from replay to replay
@@ -263,7 +283,9 @@ class GraphedForward:
     the track state lives in device memory, so it carries from replay to replay.  The warm-up and capture runs of the
     constructor are forwards like any other and advance that state: call ``model.tracker.reset()`` after construction.
     The same holds for ``model.smoother``: its launch is captured behind the tracker's, ``model.last_smooth`` holds static
-    tensors, the filter state carries across replays - call ``model.smoother.reset()`` after construction as well."""
+    tensors, the filter state carries across replays - call ``model.smoother.reset()`` after construction as well.  A
+    ``model.recalibrator``'s accumulate launch is captured behind the triangulation's and its accumulators carry across
+    replays likewise: call ``model.recalibrator.reset()`` after construction."""
 
     def __init__(self, model, meta, input_heatmaps, cameras, resize_transform, warmup=2):
         self.model = model
@@ -310,7 +332,8 @@ class PipelinedForward:
     refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
     ``model.joint_evidence``.  So is a ``model.crops``: ``crops(frames, views, ids)`` on the consumer stream, before any
     ``overlay.draw``.  And a ``model.visibility``: ``visibility(outputs[0], cameras, meta, views=views)`` there.  And a
-    ``model.triangulator``: ``triangulator(outputs[0], cameras, meta, heat_cl)`` there."""
+    ``model.triangulator``: ``triangulator(outputs[0], cameras, meta, heat_cl)`` there, and a ``model.recalibrator``:
+    ``recalibrator.accumulate(outputs[0], obs, view_state, cams, frame_set)`` behind it."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -341,6 +364,10 @@ class PipelinedForward:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.visibility = None "
                                 "and call visibility(outputs[0], cameras, meta, views=views) on the consumer stream, with "
                                 "views from model.joint_evidence(outputs[0], ...)[0]")
+        if model.recalibrator is not None:
+            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.recalibrator = None "
+                                "and call recalibrator.accumulate(outputs[0], obs, view_state, cams, frame_set) behind the "
+                                "triangulator on the consumer stream")
         if model.triangulator is not None:
             raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.triangulator = None "
                                 "and call triangulator(outputs[0], cameras, meta, heat_cl) on the consumer stream, with "

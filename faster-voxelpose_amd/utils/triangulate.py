@@ -6,7 +6,8 @@ apart from the others has been bumped.  One launch (two with the per-camera resi
 no arithmetic on tensors happens here and nothing synchronises with the host: PyTorch is used for device memory and streams
 only.
 
-Not built: bundle adjustment or re-calibration, an iterated rejection, triangulated poses fed into tracker or smoother.
+Re-calibration of a camera that has moved: ``utils/recalibrate.py::CameraRefiner`` reads ``obs`` and ``view_state``.
+Not built: an iterated rejection, triangulated poses fed into tracker or smoother.
 """
 import ctypes as C
 import math

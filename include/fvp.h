@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 18
+#define FVP_ABI_VERSION 19
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -44,6 +44,12 @@ extern "C" {
 #define FVP_TRI_OCCLUDED (-4)    /* a peak was taken, but occluder says the view does not see the joint */
 #define FVP_TRI_REJECTED (-5)    /* dropped by the rejection round */
 #define FVP_TRI_UNSOLVED (-6)    /* usable, but the joint was not triangulated: too few usable views, or degenerate */
+#define FVP_CAL_ACC 32           /* fvp_camera_refit_*: doubles of accumulator state per camera */
+/* fvp_camera_refit_solve: cal_state */
+#define FVP_CAL_OK 1             /* the step was solved and applied */
+#define FVP_CAL_CLAMPED 2        /* solved, and scaled down to the trust region before it was applied */
+#define FVP_CAL_FEW 0            /* fewer than min_obs observations: the record is copied */
+#define FVP_CAL_DEGENERATE (-1)  /* the normal matrix is not positive definite enough, or the step is not finite: copied */
 
 #define FVP_EINVAL 10001 /* bad argument (null pointer, unsupported size) */
 #define FVP_ELIMIT 10002 /* size beyond a compiled limit (see message) */
@@ -751,7 +757,7 @@ int fvp_joint_visibility(const float* fused_poses /* [B][N][J][5] */, const floa
  * One launch (two with cam_resid / cam_count), no host synchronisation, no atomics: one workgroup per (b, n), the camera
  * records in LDS, one thread per (v, j) for steps 1-6, one thread per j for steps 7-10.
  * Suggested parameters - guesses, not tuned on real data: radius 3, min_peak 0.3, undistort_iters 8, min_views 2,
- * min_det 1e-3, reject_px 0 (off).  Not built: bundle adjustment or re-calibration, an iterated rejection, triangulated
+ * min_det 1e-3, reject_px 0 (off).  Re-calibration: fvp_camera_refit_* below.  Not built: an iterated rejection, triangulated
  * poses fed into tracker or smoother by default. */
 int fvp_triangulate_joints(const float* heat_cl /* [B][V][H][W][JP] */, const float* cams /* [nsets][V][FVP_CAM_FLOATS] */,
                            int nsets, const int32_t* frame_set /* [B] */, const float* fused_poses /* [B][N][J][5] */,
@@ -762,6 +768,101 @@ int fvp_triangulate_joints(const float* heat_cl /* [B][V][H][W][JP] */, const fl
                            float* tri_stats /* [B][N][J][2] */, float* obs /* [B][V][N][J][4] */,
                            int32_t* view_state /* [B][V][N][J] */, float* cam_resid /* [B][V] */,
                            int32_t* cam_count /* [B][V] */, fvp_stream_t s);
+
+/* ---- bumped cameras re-fitted on the device (ABI 19): fvp_camera_refit_accumulate + fvp_camera_refit_solve ------------------
+ * fvp_triangulate_joints shows that a camera has moved (cam_resid); these two calls correct it.  A robust RESECTION of every
+ * camera against the 3-D joints: one Gauss-Newton step on the camera's six extrinsic parameters, the observations
+ * accumulated over as many batches as the caller likes, the step solved on the device, the result a camera record in the
+ * layout every projection call reads.  The 3-D points are held fixed - that is what pulls one bumped camera back to the
+ * consensus of the others; this is not bundle adjustment, and when every camera is re-fitted at once nothing fixes the gauge.
+ *
+ * ALL ARITHMETIC IS fp64 unless stated; every fp32 input is converted exactly; every operation is rounded on its own (no
+ * contraction); division and sqrt are IEEE; no transcendental function is used anywhere (a numpy restatement reproduces every
+ * output bit for bit: tests/recalibrate_cases.py).  dot(p,q) = (p0*q0 + p1*q1) + p2*q2.
+ *
+ * 1. fvp_camera_refit_accumulate.  points [B][N][J][5] is fused_poses or tri_poses, the caller's choice (elements 0..2 are
+ * read); obs [B][V][N][J][4] and view_state [B][V][N][J] as fvp_triangulate_joints wrote them for the same batch; cams
+ * [nsets][V][FVP_CAM_FLOATS]; frame_set [B].  acc [nsets][V][FVP_CAL_ACC] doubles is caller-owned state (as the tracker's);
+ * its initial state is all zeros:
+ *     0..20  the upper triangle of H, row-major (00, 01, ..., 05, 11, ..., 55)      21..26  g
+ *     27  sum of ww      28  sum of ww*e2      29  the number of observations (an exact integer in a double)
+ *     30  the number of observations with h < 1      31  0
+ * Observation (b,v,n,j) COUNTS for camera (s, v), s = frame_set[b], iff 0 <= s < nsets, view_state == FVP_TRI_USED,
+ * X = points[b][n][j][0:3] is finite (fabsf(x) <= FLT_MAX), ox, oy = obs[..][0:2] are finite, wf = fminf(fmaxf(obs[..][2],
+ * 0), 1) > 0 (fp32), and z > 1.0 below (the point lies more than 1 mm in front of the camera).  A NaN fails every one.
+ * For a counting observation, cm = cams[s][v] (R row-major, T, f, c, k, p):
+ *     (y0, y1) = step 5 of fvp_triangulate_joints at (ox, oy) with undistort_iters rounds, in fp32 (the same device function);
+ *     d = X - T;  xc_k = (R[3k]*d0 + R[3k+1]*d1) + R[3k+2]*d2;  z = xc_2;  iz = 1/z;  u = xc_0/z;  v = xc_1/z;
+ *     r0 = (y0 - u)*f0;  r1 = (y1 - v)*f1                         (pixels of the undistorted image)
+ *     the Jacobian of the prediction by (w, t) of the perturbation xc' = C(w) xc + t, at zero:
+ *     Ju = (f0*(-(u*v)), f0*(1 + u*u), f0*(-v), f0*iz, 0, f0*(-(u*iz)))
+ *     Jv = (f1*(-(1 + v*v)), f1*(u*v), f1*u, 0, f1*iz, f1*(-(v*iz)))
+ *     e2 = r0*r0 + r1*r1;  e = sqrt(e2);  h = (huber_px > 0 and e > huber_px) ? huber_px/e : 1;  ww = wf*h;
+ *     H_ik = H_ik + ww*((Ju_i*Ju_k) + (Jv_i*Jv_k)), i <= k;  g_i = g_i + ww*((Ju_i*r0) + (Jv_i*r1));
+ *     elements 27..30 = themselves + ww, + ww*e2, + 1, + (h < 1 ? 1 : 0).
+ * The reduction is fixed and independent of scheduling: one workgroup of 256 threads per (s, v); with q = (b*N + n)*J + j
+ * over the whole batch, thread t adds its counting entries q = t, t+256, ... in ascending order, all 31 sums from 0; the 256
+ * partial vectors fold as p[t] = p[t] + p[t+h] for h = 128, 64, ..., 1; then acc[s][v][i] = acc[s][v][i]*double(decay) +
+ * p[0][i] for i < 31, and element 31 is written as 0.  decay = 1 accumulates, 0 < decay < 1 forgets, 0 replaces (the old
+ * content must be finite: NaN*0 is NaN).  Every camera of the table is updated by every call (a camera without a counting
+ * observation decays).  The accumulators are a linearisation AT cams: after a camera's record changes, its row of acc must
+ * be zeroed by the caller before the next accumulation.
+ * FVP_EINVAL: a null pointer; B < 0; V, N, J or nsets < 1; undistort_iters < 0; huber_px not finite; decay not in [0, 1].
+ * FVP_ELIMIT: V > FVP_MAX_VIEWS, J > FVP_MAX_JOINTS, undistort_iters > 16, B*N*J > INT_MAX.  B == 0 returns 0 without a
+ * launch (acc does not decay).  One launch, no atomics.
+ *
+ * 2. fvp_camera_refit_solve, one thread per camera (s, v), a = acc[s][v], cm = cams_in[s][v]; lambda, min_pivot,
+ * max_angle_rad and max_shift_mm converted to double:
+ *     count = a[29].  Not count >= min_obs: state FVP_CAL_FEW.
+ *     D_i = sqrt(H_ii).  Any H_ii not > 0: FVP_CAL_DEGENERATE.
+ *     A_ik = H_ik/(D_i*D_k), and A_ii = H_ii/(D_i*D_i) + lambda         (Jacobi scaling: radians against millimetres put
+ *     the unscaled matrix at a condition of ~1e9).
+ *     Cholesky A = L L^T column by column, j = 0..5, every sum left to right in ascending k:
+ *         piv_j = A_jj - L_j0*L_j0 - ... - L_j,j-1*L_j,j-1;  L_jj = sqrt(piv_j);
+ *         L_ij = (A_ij - L_i0*L_j0 - ... - L_i,j-1*L_j,j-1)/L_jj, i = j+1..5.
+ *     Any piv_j not > min_pivot (a NaN fails): DEGENERATE.  The threshold is unit-free because of the scaling.
+ *     minpiv: from piv_0, replaced by piv_j iff piv_j < minpiv, j ascending.
+ *     Forward  y_i = (g_i/D_i - L_i0*y_0 - ... - L_i,i-1*y_i-1)/L_ii, i = 0..5;
+ *     back     zeta_i = (y_i - L_i+1,i*zeta_i+1 - ... - L_5,i*zeta_5)/L_ii, i = 5..0;   delta_i = zeta_i/D_i;
+ *     w = delta[0:3] (radians), t = delta[3:6] (mm);  theta = sqrt(dot(w,w)), sigma = sqrt(dot(t,t)).
+ *     theta or sigma not finite (not <= DBL_MAX): DEGENERATE.
+ *     gd = ((((g0*delta0 + g1*delta1) + g2*delta2) + g3*delta3) + g4*delta4) + g5*delta5      (before the clamp)
+ *     Trust region: kappa = 1;  if theta > max_angle_rad: kappa = max_angle_rad/theta;  if sigma > max_shift_mm and
+ *     max_shift_mm/sigma < kappa: kappa = max_shift_mm/sigma.  If kappa < 1: delta_i = delta_i*kappa, theta and sigma are
+ *     computed again from it, state FVP_CAL_CLAMPED; else FVP_CAL_OK.
+ *     Cayley retraction: h = 0.5*w;  n = sqrt(1 + dot(h,h));  qw = 1/n, qx = h0/n, qy = h1/n, qz = h2/n;
+ *         C00 = 1 - 2*(qy*qy + qz*qz)   C01 = 2*(qx*qy - qz*qw)       C02 = 2*(qx*qz + qy*qw)
+ *         C10 = 2*(qx*qy + qz*qw)       C11 = 1 - 2*(qx*qx + qz*qz)   C12 = 2*(qy*qz - qx*qw)
+ *         C20 = 2*(qx*qz - qy*qw)       C21 = 2*(qy*qz + qx*qw)       C22 = 1 - 2*(qx*qx + qy*qy)
+ *     R'_ik = (C_i0*R_0k + C_i1*R_1k) + C_i2*R_2k;   T'_k = T_k - ((R'_0k*t0 + R'_1k*t1) + R'_2k*t2)   (R' before its rounding);
+ *     R' and T' are each rounded to fp32 once; the other 12 floats of the record are copied.
+ * cams_out [nsets][V][FVP_CAM_FLOATS] (must not be cams_in): in the states FEW and DEGENERATE a copy of the cams_in record.
+ * cal_stats [nsets][V][6] fp32 or NULL: (theta, sigma - after the clamp -, rms_before = sqrt(a[28]/a[27]), rms_pred =
+ * sqrt(max(0, a[28] - gd)/a[27]), count, minpiv), each rounded to fp32 once; max(0, x) = x > 0 ? x : 0.  In the states FEW and
+ * DEGENERATE: (0, 0, rms_before, 0, count, 0); rms_before and rms_pred are 0 unless a[27] > 0.  rms_pred is the residual the
+ * linear model expects after the step; it is exact only for lambda = 0 and kappa = 1.
+ * cal_state [nsets][V] int32 or NULL: FVP_CAL_OK, FVP_CAL_CLAMPED, FVP_CAL_FEW, FVP_CAL_DEGENERATE.
+ * FVP_EINVAL: a null acc, cams_in or cams_out; cams_out == cams_in; nsets or V < 1; min_obs < 6; lambda not >= 0 or not
+ * finite; min_pivot, max_angle_rad or max_shift_mm not > 0 or not finite.  FVP_ELIMIT: V > FVP_MAX_VIEWS.
+ * Both calls: every pointer is a device pointer, nothing is allocated, no host synchronisation, capturable; nothing is
+ * written when an error is returned.  One Gauss-Newton round is accumulate + solve; for another round zero acc and
+ * accumulate against cams_out (obs are pixels and do not depend on the camera table).
+ * Suggested parameters - guesses, not tuned on real data: undistort_iters 8, huber_px 0 (off), decay 1, min_obs 60,
+ * lambda 0, min_pivot 1e-9, max_angle_rad 0.087 (5 degrees), max_shift_mm 200.  Not built: intrinsics or lens re-fit, joint
+ * refinement of points and cameras (bundle adjustment), gauge fixing when every camera is re-fitted at once, automatic
+ * adoption of the corrected cameras into an engine. */
+int fvp_camera_refit_accumulate(const float* points /* [B][N][J][5] */, const float* obs /* [B][V][N][J][4] */,
+                                const int32_t* view_state /* [B][V][N][J] */,
+                                const float* cams /* [nsets][V][FVP_CAM_FLOATS] */, int nsets,
+                                const int32_t* frame_set /* [B] */, int B, int V, int N, int J, int undistort_iters,
+                                float huber_px, float decay, double* acc /* [nsets][V][FVP_CAL_ACC] in/out */,
+                                fvp_stream_t s);
+int fvp_camera_refit_solve(const double* acc /* [nsets][V][FVP_CAL_ACC] */,
+                           const float* cams_in /* [nsets][V][FVP_CAM_FLOATS] */, int nsets, int V, int min_obs,
+                           float lambda, float min_pivot, float max_angle_rad, float max_shift_mm,
+                           float* cams_out /* [nsets][V][FVP_CAM_FLOATS], not cams_in */,
+                           float* cal_stats /* [nsets][V][6] or NULL */, int32_t* cal_state /* [nsets][V] or NULL */,
+                           fvp_stream_t s);
 
 /* ---- "next" row f-1: Pose-ResNet backbone in bf16 (lib/models/resnet.py:98-215) ------------------------
  * Activations are NHWC bf16 (uint16 storage; the image input is padded to 8 channels), every conv /

@@ -1572,6 +1572,16 @@ extern "C" int fvp_triplane_max(const float* cubes, float* planes, int nP, int J
   return launch_status();
 }
 
+// y segments per x strip of the owned fused projection (k_project_triplane_own): a shape rule, nothing read from the
+// device.  The grid is ceil(C / 4) strips x ny x nP workgroups, of which a window of w x h fine voxels uses
+// ceil(w / 4) x min(ny, ceil(h / 4)).  Measured (profiles/triplane_owned.txt; us per launch, block form 339-341 / Shelf 480 /
+// Campus 152): the kernel lives on many small workgroups per CU - whole strips (ny = 1) take 629 us (Shelf 788), ny = 2
+// 339-348 (534, 225), ny = 4 350 (499, 148), ny = 8 345-350 (475, 147), and one y block per workgroup (ny = C / 4 = 16)
+// 327-329 (460, 144-146): the only setting below the block form on all three, so the rule is a function of C alone.  (Coarser
+// segments would let a workgroup store its x-z cells without atomics; the imbalance of long strips costs more than that.
+// Coarser counts are reachable through FVP_TRI_NY in the diagnostics build only.)
+static int tri_owned_ny(int C) { return ceil_div(C, kBY); }
+
 extern "C" int fvp_project_individual_triplane(const float* heat_cl, const float* cams, const int32_t* frame_set,
                                                const int32_t* person_frame, const uint8_t* person_valid,
                                                const int32_t* boxes, const float* fx, const float* fy,
@@ -1589,9 +1599,11 @@ extern "C" int fvp_project_individual_triplane(const float* heat_cl, const float
   [[maybe_unused]] const int chunks = ceil_div(C * C, 256);      // (the diagnostics build's gather form)
   const int nvl = ceil_div(g->JP, 16);
   ProfScope ps(FVP_K_PROJECT_TRIPLANE, as_stream(s));
-  // The shipped form for every joint count (JP <= 32) is the UNSTAGED compact-block kernel k_project_triplane_blk (round 4:
-  // Panoptic 494 -> 348 us, Shelf 709 -> 592 us, Campus 161 -> 158 us against the LDS-staged forms, same bits; lanes whose
-  // channel quad lies beyond JP idle, so miniature joint counts run it too).  The LDS-staged quad / lane-per-voxel forms
+  // The shipped forms for every joint count (JP <= 32) are UNSTAGED: the owned form k_project_triplane_own wherever its LDS
+  // cells fit (below: Panoptic 339-341 -> 327-329 us, Shelf 480 -> 460-461 us, Campus 152 -> 144-146 us against the block
+  // form, same bits), else the compact-block kernel k_project_triplane_blk (round 4: Panoptic 494 -> 348 us, Shelf 709 ->
+  // 592 us, Campus 161 -> 158 us against the LDS-staged forms, same bits; lanes whose channel quad lies beyond JP idle, so
+  // miniature joint counts run them too).  The LDS-staged quad / lane-per-voxel forms
   // and the round-1 gather form exist in the diagnostics build only (round 6), behind FVP_TRIPLANE_STAGED / _LANE /
   // _QUAD / _GATHER; they give the same bits (tests/test_emu_kernels.py, tools/gpu_switch_matrix.sh).
   const int F0 = fine_grid ? fine[0] : 0, F1 = fine_grid ? fine[1] : 0, F2 = fine_grid ? fine[2] : 0;
@@ -1665,6 +1677,40 @@ extern "C" int fvp_project_individual_triplane(const float* heat_cl, const float
 #else
     constexpr bool zres = false;
 #endif
+    // The OWNED form (k_project_triplane_own, fvp_project_lds.h): x strips that keep their x-y maxima in registers and their
+    // x-z cells in LDS; only y-z is merged through global atomics.  Taken wherever its cells fit kTriOwnMaxLds (36 KB: C <= 32,
+    // and C = 64 up to JP = 20); beyond that (C = 64 with JP >= 24: 37.5 KB; C >= 128: 42.5 KB and more leave three workgroups per
+    // CU, panoptic128 measured 559 -> 523 frames/s) the block form below stays.  The kernel addresses one frame's heatmaps
+    // and one camera set's coordinate cache with 32-bit offsets, so shapes whose H * W * JP * V or F0 * F1 * F2 * V do not fit
+    // 31 bits keep the block form too (its offsets are 64-bit).  The
+    // diagnostics build keeps the block form selectable: FVP_TRI_OWNED=0 (FVP_TRI_ZRES=1 implies it), and FVP_TRI_NY=n
+    // overrides the segment count.  Same bits either way.
+    const bool fits32 = (long long)g->H * g->W * g->JP * g->V <= INT_MAX && (long long)F0 * F1 * F2 * g->V <= INT_MAX;
+    bool owned = tri_owned_lds(C, g->JP) <= kTriOwnMaxLds && fits32 && !zres;
+    int ny = tri_owned_ny(C);
+#if FVP_DIAG
+    if (const char* e = fvp::diag_env("FVP_TRI_OWNED")) owned = owned && atoi(e) != 0;      // read per call: tests switch it
+    if (const char* e = fvp::diag_env("FVP_TRI_NY")) {
+      const int v = atoi(e), top = ceil_div(C, kBY);
+      ny = v < 1 ? 1 : (v > top ? top : v);
+    }
+#endif
+    if (owned) {
+      const int nsx = ceil_div(C, kOwnSX);
+      int zsh_o = 0;
+      while ((1 << zsh_o) < C || (1 << zsh_o) < kOwnBZ) ++zsh_o;
+      const size_t lds_o = tri_owned_lds(C, g->JP);
+      const bool q5o = nvl == 2 && g->JP == 20 && fvp::diag_env("FVP_TRI_NO_Q5") == nullptr;
+#define CALLO(NVL_, CACHED_, Q5_)                                                                                            \
+  hipLaunchKernelGGL((k_project_triplane_own<NVL_, CACHED_, Q5_>), dim3(nsx * ny * nP), dim3(kOwnThreads), lds_o,           \
+                     as_stream(s), heat_cl, reinterpret_cast<const Cam*>(cams), frame_set, person_frame, person_valid, boxes, \
+                     fx, fy, fz, C, nP, nsx, ny, ppf, *g, fine_grid, F0, F1, F2, planes, zsh_o)
+      if (q5o) { if (fine_grid) CALLO(2, true, true); else CALLO(2, false, true); }
+      else if (nvl == 2) { if (fine_grid) CALLO(2, true, false); else CALLO(2, false, false); }
+      else { if (fine_grid) CALLO(1, true, false); else CALLO(1, false, false); }
+#undef CALLO
+      return launch_status();
+    }
     const size_t lds_b = zres ? lds_z : size_t(kBlkBX * kBY + (kBlkBX + kBY) * bz) * (g->JP + 1) * 4;   // cell pitch JP + 1
 #define CALLB(NVL_, CACHED_, ZRES_)                                                                                          \
   hipLaunchKernelGGL((k_project_triplane_blk<NVL_, CACHED_, ZRES_>), dim3(nbx2 * nby * nP), dim3(kBlkThreads), lds_b,       \

@@ -469,7 +469,8 @@ k_project_triplane_lds(const float* __restrict__ heat_cl, const Cam* __restrict_
 #endif
 // Block shape, measured (80 people, same box): 8 x 4 x 32 voxels / 512 threads 396 us; 4 x 4 x 32 / 256 threads 363 us (more,
 // smaller workgroups per CU: the plane-maxima phase of one lies beside the sampling of the others); 2 x 4 x 32 410 us;
-// 4 x 4 x 16 346-352 us.  Ablations of the 8 x 4 x 32 form: 395 us = 247 us sampling (10.5 GB of 64-byte taps: the L1's
+// 4 x 4 x 16 346-352 us (339-341 us on the boxes of profiles/triplane_owned.txt, where the owned form below, which the
+// shipped library launches instead wherever its cells fit, takes 327-329 us).  Ablations of the 8 x 4 x 32 form: 395 us = 247 us sampling (10.5 GB of 64-byte taps: the L1's
 // 64 B/clk/CU line rate gives 268 us) + 81 us plane maxima + 67 us coordinates / tap descriptors.
 #ifndef FVP_TRI_BLK_BZ
 #define FVP_TRI_BLK_BZ 16
@@ -796,6 +797,343 @@ k_project_triplane_blk(const float* __restrict__ heat_cl, const Cam* __restrict_
             plane_max(&pyz[size_t(ch) * CC + (gy0 + a - kBX - tl1) * C + lz0 + z], vv);
           }
         }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The OWNED form: a workgroup owns the plane cells it can.  k_project_triplane_blk merges all three plane tiles of every
+// 4 x 4 x 16 block into HBM with global atomicMax (each plane cell is touched ~2.6 times: 153 MB written per launch for
+// 59 MB of planes) and pays a zero fill, three barriers and two merge loops per z block.  Here a work unit is an X STRIP of
+// one person's window: kOwnSX columns of x, a contiguous segment of the window's y blocks (all of them when ny == 1), and
+// the whole z range.  The workgroup walks the segment's y blocks and, inside each, its z blocks; every (x, y, z block) is
+// sampled exactly as in k_project_triplane_blk (block shape, lane mapping, quad broadcast, next-view coordinate prefetch,
+// Q5), so the planes keep their bits (max is order-independent).
+//   x-y  a lane's column maximum stays in registers across the z loop and is written with ONE PLAIN STORE per cell at the
+//        end of the column (after clamp(v / V, 0, 1)): no LDS cells, no atomics - the workgroup is the only one that sees
+//        the column.
+//   x-z  the strip's cells [kOwnSX][zt][JP + 1] stay in LDS for the whole strip (17 KB at 64 z and JP = 16, against the
+//        35-43 KB of ZRES): zero-filled once, LDS atomicMax from every y block, written once at the end - with plain stores
+//        when the workgroup has seen every y of the window (ny == 1), with plane_max when the strip is segmented.
+//   y-z  per-block cells [kBY][16][JP + 1], merged into the global plane with plane_max across the person's strips: the one
+//        plane that still needs global atomics, and whose cells inside the window still rely on the zero fill (cells
+//        outside [s, e) are never written by any plane here: the caller's zero fill of `planes` is part of the contract).
+//        The cells are DOUBLE-BUFFERED: block k's atomics go to buffer k & 1, one barrier, then the merge loop reads the
+//        buffer and puts back the zeros it found missing.  The next writer of that buffer (block k + 2) is separated from
+//        the merge by the barrier of block k + 1, so a z block costs one barrier and no zero fill.
+// Grid: ceil(C / kOwnSX) x ny x nP, fixed at launch; a workgroup whose strip or segment is empty exits (as the block form
+// does).  ny is a function of the shape alone (tri_owned_ny in fvp_project.hip).
+// Constants, from the runs in profiles/triplane_owned.txt (us per launch: Panoptic 80 people / Shelf / Campus; block form
+// 339-341 / 480 / 152): kOwnSX = 4 is the x extent of the lane mapping; ny = 1 (whole strips, x-z stored without atomics)
+// 629 / 788 - 560-1 280 long workgroups leave the CUs' L1s idle; ny = 2: 339-348 / 534 / 225; 4: 350 / 499 / 148; 8: 345-350 /
+// 475 / 147; ny = C / 4 = 16 (one y block per workgroup): 327-329 / 460-461 / 144-146.  Only the last is below the block form
+// everywhere, so the rule is ny = C / 4: what the form then saves is the per-z-block zero fill, two of three barriers, the
+// x-y cells' LDS round trip and global atomics, and three quarters of the workgroup launches.  At that rule the resident
+// x-z cells OWN NOTHING: every x-z cell still receives one global plane_max per y block, the same count as in the block
+// form (whose z blocks merge disjoint x-z cells); only the merge loops fall from one per z block to one per column.  The fall
+// in written bytes (156 -> 117 MB per launch) is the x-y plane.  The residency ([4][C] cells, 17 KB) and the plain-store
+// branch serve the coarser segmentations of the diagnostics build, and the residency is why C >= 128 and C = 64 with
+// JP >= 24 exceed the LDS limit and keep the block form; per-block, double-buffered x-z cells like y-z would fit every shape
+// and are the next step here (not built: unmeasured).
+// Registers: scalars that only the merge phases need (plane origins, C, J, the segment's end ...) wait in 11 words of LDS
+// and are re-read there; kept in SGPRs across the sampling loops they cost 10-41 spilled registers in five of the six forms.
+constexpr int kOwnSX = 4;                               // x columns of a strip = the x extent of the lane mapping
+constexpr int kOwnBZ = 16;                              // z block
+constexpr int kOwnThreads = kOwnSX * kBY * 4 * 4;      // 256
+#ifndef FVP_TRI_OWN_MAX_KB
+#define FVP_TRI_OWN_MAX_KB 36   // C = 128 (42.5 KB of cells at JP = 16: three workgroups per CU) measured slower: 559 -> 523 frames/s
+#endif
+constexpr size_t kTriOwnMaxLds = size_t(FVP_TRI_OWN_MAX_KB) * 1024;
+constexpr int kOwnPar = 16;                             // words of merge-phase values behind the cells (11 used)
+// LDS bytes of a workgroup: the strip's x-z cells over zt = max(C, 16) z cells + two y-z block buffers, cell pitch JP + 1
+inline size_t tri_owned_lds(int C, int JP) {
+  const int zt = C > kOwnBZ ? C : kOwnBZ;
+  return (size_t(kOwnSX) * zt + 2 * size_t(kBY) * kOwnBZ) * size_t(JP + 1) * 4 + 4 * kOwnPar;   // + the merge-phase values
+}
+
+template <int NVL, bool CACHED, bool Q5 = false>
+__global__ void __launch_bounds__(kOwnThreads, FVP_TRI_BLK_OCC)
+k_project_triplane_own(const float* __restrict__ heat_cl, const Cam* __restrict__ cams, const int* __restrict__ frame_set,
+                       const int* __restrict__ person_frame, const uint8_t* __restrict__ person_valid,
+                       const int* __restrict__ boxes, const float* __restrict__ fx, const float* __restrict__ fy,
+                       const float* __restrict__ fz, int C, int nP, int nsx, int ny, int ppf, FvpGeom g,
+                       const float* __restrict__ fgrid, int F0, int F1, int F2, float* __restrict__ planes, int zsh) {
+  static_assert(!Q5 || NVL == 2, "the five-quad form replaces the two-group form");
+  constexpr int NVA = Q5 ? 1 : NVL;                  // quad groups sampled by the broadcast passes
+  constexpr int BZ = kOwnBZ, VPT = BZ / 4, OWN = VPT / 4, SX = kOwnSX, NT = kOwnThreads;
+  HIP_DYNAMIC_SHARED(float, smem)
+  const int J = g.J, JP = g.JP, V = g.V, W = g.W, H = g.H;
+  int p, blk;
+  {
+    const int id = blockIdx.x;
+    const int bpp = nsx * ny, bpf = ppf * bpp;
+    const int nframes = nP / ppf;
+    if (nframes % 8 == 0) {
+      const int xcd = id & 7, j = id >> 3;
+      const int frame = xcd + 8 * (j / bpf), r = j % bpf;
+      p = frame * ppf + r / bpp;
+      blk = r % bpp;
+    } else {
+      p = id / bpp;
+      blk = id % bpp;
+    }
+  }
+  if (person_valid && !person_valid[p]) return;
+  const int* bx = boxes + p * 9;
+  const int tl0 = bx[0], tl1 = bx[1], tl2 = bx[2];
+  const int zt = 1 << zsh;                                               // z cells of an x-z row in LDS (>= C, >= BZ)
+  const int s0 = bx[3], s1 = bx[4], s2 = bx[5], e0 = bx[6], e1 = bx[7], e2 = imin(bx[8], s2 + zt);
+  if (s0 >= e0 || s1 >= e1 || s2 >= e2) return;
+  const int xs = blk / ny, seg = blk - xs * ny;
+  const int gx0 = s0 + xs * SX;                                          // strips are aligned to the window start
+  if (gx0 >= e0) return;
+  // the strip's y blocks: segment `seg` of ny contiguous segments of ceil(blocks / ny) blocks (uneven when ny does not
+  // divide the count; the last ones may be empty).  yend bounds the segment's columns: e1 for the last segment.
+  const int nyb = (e1 - s1 + kBY - 1) / kBY, per = (nyb + ny - 1) / ny;
+  if (seg * per >= nyb) return;
+  const int ybeg = s1 + seg * per * kBY, yend = imin(ybeg + per * kBY, e1);
+
+  const int t = threadIdx.x, q = t & 3;
+  const int slot = t >> 2, zs = slot & 3, yy = (slot >> 2) & (kBY - 1), xx = slot / (4 * kBY);
+  const int gxi = gx0 + xx;
+  const bool x_in = gxi < e0;
+  const int b = person_frame[p], set = frame_set[b];
+  // 32-bit strides inside one frame's heatmaps / one camera set's coordinate cache (the launcher takes this form only when
+  // H * W * JP * V and F0 * F1 * F2 * V fit 31 bits): uniform 64-bit bases per view, one 32-bit offset per lane
+  const int view_stride = H * W * JP;
+  const float* frame = heat_cl + size_t(b) * V * view_stride;
+  const Cam* cm = cams + size_t(set) * V;
+  const float wx = x_in ? fx[gxi] : 0.0f;
+  const int nfine = F0 * F1 * F2;
+  const float2* gset = CACHED ? reinterpret_cast<const float2*>(fgrid) + size_t(set) * V * nfine : nullptr;
+  const int JPp = JP + 1;                                               // cell pitch: odd, conflict-free (see the block form)
+  int* rxz = reinterpret_cast<int*>(smem);                               // [SX][zt][JPp]: the strip's x-z cells
+  int* ryz = rxz + ((SX << zsh) * JPp);                                  // [2][kBY][BZ][JPp]: y-z cells of a block, two buffers
+  constexpr int kYzCells = kBY * BZ;
+  // Values only the merge phases and the loop heads need wait in LDS instead of in scalar registers held across the sampling
+  // loops (kOwnPar words): [0] person, [1..3] origin of the window in the x-y / x-z / y-z plane, [4] gx0, [5] e0, [6] s2,
+  // [7] end of the segment's y range, [8] C, [9] J, [10] ny.  Written once, before the first barrier; uniform reads.
+  static_assert(kOwnPar >= 11, "merge-phase values");
+  int* par = ryz + 2 * kYzCells * JPp;
+  {
+    const int ncell = ((SX << zsh) + 2 * kYzCells) * JPp;
+    for (int i = t; i < ncell; i += NT) rxz[i] = 0;
+    if (t == 0) {
+      par[0] = p;
+      par[1] = tl0 * C + tl1;
+      par[2] = tl0 * C + tl2;
+      par[3] = tl1 * C + tl2;
+      par[4] = gx0;
+      par[5] = e0;
+      par[6] = s2;
+      par[7] = yend;
+      par[8] = C;
+      par[9] = J;
+      par[10] = ny;
+    }
+  }
+  __syncthreads();
+  auto parv = [&](int i) { return __builtin_amdgcn_readfirstlane(par[i]); };
+  auto plane = [&](int person, int k) { return planes + (size_t(person) * 3 + k) * parv(9) * parv(8) * parv(8); };
+
+  int kb = 0;                                                            // blocks done: selects the y-z buffer
+  for (int gy0 = ybeg; gy0 < parv(7); gy0 += kBY) {
+    const int gyi = gy0 + yy;
+    const bool col_in = x_in && gyi < parv(7);
+    const float wy = col_in ? fy[gyi] : 0.0f;
+    const unsigned colo = unsigned((col_in ? gxi : 0) * F1 + (col_in ? gyi : 0)) * unsigned(F2);   // this lane's column in a view's grid
+    float mcol[NVA][4];                                                  // this lane's share of its column's x-y maxima
+#pragma unroll
+    for (int n = 0; n < NVA; ++n)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) mcol[n][c] = 0.0f;
+    [[maybe_unused]] float mcol5[4] = {0.0f, 0.0f, 0.0f, 0.0f};          // Q5: channels 16-19 (voxels 4 k + q)
+
+    for (int gz0 = parv(6); gz0 < e2; gz0 += BZ, ++kb) {
+      float acc[VPT][NVA][4];
+#pragma unroll
+      for (int i = 0; i < VPT; ++i)
+#pragma unroll
+        for (int n = 0; n < NVA; ++n)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[i][n][c] = 0.0f;
+      [[maybe_unused]] float accx[OWN][1][4];                            // Q5: channels 16-19 of voxel 4 k + q
+#pragma unroll
+      for (int kk = 0; kk < OWN; ++kk)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) accx[kk][0][c] = 0.0f;
+      float2 crd[OWN];
+      auto load_coords = [&](int v) {
+#pragma unroll
+        for (int k = 0; k < OWN; ++k) {
+          const int gzi = gz0 + zs + 4 * (q + 4 * k);
+          crd[k] = (gset + size_t(v) * nfine)[colo + unsigned(gzi < F2 ? gzi : F2 - 1)];
+        }
+      };
+      if (CACHED) load_coords(0);
+      for (int v = 0; v < V; ++v) {
+        // this lane's own voxels (i = q + 4 k) of view v: tap descriptor relative to the view's plane
+        TapL mine[OWN];
+#pragma unroll
+        for (int k = 0; k < OWN; ++k) {
+          const int gzi = gz0 + zs + 4 * (q + 4 * k);
+          const bool vin = col_in && gzi < e2;
+          TapL d;
+          d.base = d.dx = d.dy = 0;
+          d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0.0f;
+          if (vin) {
+            float sx, sy;
+            if (CACHED) {
+              sx = crd[k].x;
+              sy = crd[k].y;
+            } else {
+              project_norm(cm[v], g, wx, wy, fz[gzi], sx, sy);
+            }
+            int x0, y0, inside;
+            float w4[4];
+            tap_origin(sx, sy, W, H, x0, y0, w4, inside);
+            const int cx0 = imin(imax(x0, 0), W - 1), cx1 = imin(imax(x0 + 1, 0), W - 1);
+            const int cy0 = imin(imax(y0, 0), H - 1), cy1 = imin(imax(y0 + 1, 0), H - 1);
+            d.base = (cy0 * W + cx0) * JP;
+            d.dx = (cx1 - cx0) * JP;
+            d.dy = (cy1 - cy0) * W * JP;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) d.w[c] = ((inside >> c) & 1) ? w4[c] : 0.0f;
+          }
+          mine[k] = d;
+        }
+        if (CACHED && v + 1 < V) load_coords(v + 1);   // next view's coordinates under this view's sampling
+        const float* gsrc = frame + size_t(v) * view_stride;
+        auto sample = [&](const TapL& tv, auto& a, auto own) {
+          constexpr bool kOwn = decltype(own)::value;                    // Q5's extra pass: channels 16-19, every lane
+#pragma unroll
+          for (int n = 0; n < (kOwn ? 1 : NVA); ++n) {
+            const int ch0 = kOwn ? 16 : 16 * n + 4 * q;
+            if (kOwn || ch0 < JP) {
+              const float* p0 = gsrc + tv.base + ch0;
+              const float4 v0 = glb_ld4(p0), v1 = glb_ld4(p0 + tv.dx), v2 = glb_ld4(p0 + tv.dy), v3 = glb_ld4(p0 + tv.dy + tv.dx);
+              const f32x2 w0 = f32x2{tv.w[0], tv.w[0]}, w1 = f32x2{tv.w[1], tv.w[1]}, w2 = f32x2{tv.w[2], tv.w[2]},
+                          w3 = f32x2{tv.w[3], tv.w[3]};
+              f32x2 lo = f32x2{v0.x, v0.y} * w0, hi = f32x2{v0.z, v0.w} * w0;
+              lo = __builtin_elementwise_fma(f32x2{v1.x, v1.y}, w1, lo);
+              hi = __builtin_elementwise_fma(f32x2{v1.z, v1.w}, w1, hi);
+              lo = __builtin_elementwise_fma(f32x2{v2.x, v2.y}, w2, lo);
+              hi = __builtin_elementwise_fma(f32x2{v2.z, v2.w}, w2, hi);
+              lo = __builtin_elementwise_fma(f32x2{v3.x, v3.y}, w3, lo);
+              hi = __builtin_elementwise_fma(f32x2{v3.z, v3.w}, w3, hi);
+              const f32x2 alo = f32x2{a[n][0], a[n][1]} + lo, ahi = f32x2{a[n][2], a[n][3]} + hi;
+              a[n][0] = alo.x; a[n][1] = alo.y; a[n][2] = ahi.x; a[n][3] = ahi.y;
+            }
+          }
+        };
+#pragma unroll
+        for (int k = 0; k < OWN; ++k) {
+          { const TapL tv = quad_bcast_l<0>(mine[k]); sample(tv, acc[4 * k + 0], std::false_type{}); }
+          { const TapL tv = quad_bcast_l<1>(mine[k]); sample(tv, acc[4 * k + 1], std::false_type{}); }
+          { const TapL tv = quad_bcast_l<2>(mine[k]); sample(tv, acc[4 * k + 2], std::false_type{}); }
+          { const TapL tv = quad_bcast_l<3>(mine[k]); sample(tv, acc[4 * k + 3], std::false_type{}); }
+          if constexpr (Q5) sample(mine[k], accx[k], std::true_type{});
+        }
+      }
+      // ---- maxima over the RAW view sums (clamped at 0: they order like ints; mean + clamp once per plane cell, as in the
+      //      block form): x-y into the lane's registers, x-z into the strip's resident cells, y-z into this block's buffer
+      int* cyz = ryz + (kb & 1) * (kYzCells * JPp);
+      const int zb = gz0 - parv(6) + zs;                                      // (z >= e2 - s2 only for voxels outside the window: val = 0)
+#pragma unroll
+      for (int n = 0; n < NVA; ++n)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int ch = 16 * n + 4 * q + c;
+#pragma unroll
+          for (int i = 0; i < VPT; ++i) {
+            const float val = fmaxf(acc[i][n][c], 0.0f);
+            mcol[n][c] = fmaxf(mcol[n][c], val);
+            if (val > 0.0f && ch < JP) {
+              atomicMax(&rxz[((xx << zsh) + zb + 4 * i) * JPp + ch], __float_as_int(val));
+              atomicMax(&cyz[(yy * BZ + zs + 4 * i) * JPp + ch], __float_as_int(val));
+            }
+          }
+        }
+      if constexpr (Q5) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int ch = 16 + c;
+#pragma unroll
+          for (int kk = 0; kk < OWN; ++kk) {
+            const float val = fmaxf(accx[kk][0][c], 0.0f);
+            mcol5[c] = fmaxf(mcol5[c], val);
+            if (val > 0.0f) {
+              const int i = 4 * kk + q;
+              atomicMax(&rxz[((xx << zsh) + zb + 4 * i) * JPp + ch], __float_as_int(val));
+              atomicMax(&cyz[(yy * BZ + zs + 4 * i) * JPp + ch], __float_as_int(val));
+            }
+          }
+        }
+      }
+      __syncthreads();                                                   // this block's y-z maxima are in
+      float* pyz = plane(parv(0), 2) - parv(3);                            // (the window's origin folded in)
+      const float nv = float(V);
+      const int Jm = parv(9), Cm = parv(8), CCm = Cm * Cm, yendm = parv(7);
+      for (int i = t; i < kYzCells * Jm; i += NT) {                       // y-z rows, z fastest
+        static_assert(kYzCells == 64 && BZ == 16, "index arithmetic below");
+        const int ch = i >> 6, r = i & 63, a = r >> 4, z = r & 15;
+        const int raw = cyz[r * JPp + ch];
+        if (raw > 0) {
+          cyz[r * JPp + ch] = 0;                                         // (channels J .. JP - 1 are never read: left as they are)
+          if (gz0 + z < e2 && gy0 + a < yendm) {
+            const int vv = __float_as_int(clampf(__fdiv_rn(__int_as_float(raw), nv), 0.0f, 1.0f));
+            if (vv > 0) plane_max(&pyz[size_t(ch) * CCm + (gy0 + a) * Cm + gz0 + z], vv);
+          }
+        }
+      }
+    }
+    // ---- the column is complete: x-y cells, one plain store each (the four zs lanes of a column sit 4 lanes apart inside
+    //      one DPP row: rotate by 4 and 8; all lanes are active here - the loop bounds are workgroup-uniform)
+    // (jl: the channel limit of the lanes that store - depends on the y block, so the compiler keeps no mask per channel
+    //  alive across the loops)
+    const int Cx = parv(8), CCx = Cx * Cx;
+    const int jl = (zs == 0 && col_in) ? parv(9) : 0;
+    float* pxy = plane(parv(0), 0) - parv(1) + (gxi * Cx + gyi);
+    const float nv = float(V);
+#pragma unroll
+    for (int n = 0; n < NVA; ++n)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int ch = 16 * n + 4 * q + c;
+        int mi = __float_as_int(mcol[n][c]);                             // non-negative floats order like ints
+        mi = imax(mi, dpp_i<0x124>(mi));
+        mi = imax(mi, dpp_i<0x128>(mi));
+        if (ch < jl) pxy[size_t(ch) * CCx] = clampf(__fdiv_rn(__int_as_float(mi), nv), 0.0f, 1.0f);
+      }
+    if constexpr (Q5) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {                                      // the fifth quad: over all 16 lanes of the row (q and zs)
+        const int ch = 16 + c;
+        int mi = __float_as_int(mcol5[c]);
+        mi = imax(mi, dpp_i<0x121>(mi));
+        mi = imax(mi, dpp_i<0x122>(mi));
+        mi = imax(mi, dpp_i<0x124>(mi));
+        mi = imax(mi, dpp_i<0x128>(mi));
+        if (q == 0 && ch < jl) pxy[size_t(ch) * CCx] = clampf(__fdiv_rn(__int_as_float(mi), nv), 0.0f, 1.0f);
+      }
+    }
+  }
+  // ---- the strip's x-z cells: every y block of the segment is in
+  __syncthreads();
+  {
+    const int s2t = parv(6), nz = e2 - s2t, sgx0 = parv(4), se0 = parv(5), Jt = parv(9), Ct = parv(8), CCt = Ct * Ct, nyt = parv(10);
+    float* pxz = plane(parv(0), 1) - parv(2) + s2t;
+    const float nv = float(V);
+    for (int i = t; i < (SX << zsh) * Jt; i += NT) {                      // z fastest
+      static_assert(SX == 4, "index arithmetic below");
+      const int ch = i >> (zsh + 2), r = i & ((SX << zsh) - 1), a = r >> zsh, z = r & (zt - 1);
+      if (z < nz && sgx0 + a < se0) {
+        const int raw = rxz[r * JPp + ch];
+        const int vv = raw > 0 ? __float_as_int(clampf(__fdiv_rn(__int_as_float(raw), nv), 0.0f, 1.0f)) : 0;
+        float* cell = &pxz[size_t(ch) * CCt + (sgx0 + a) * Ct + z];
+        if (nyt == 1) *cell = __int_as_float(vv);                         // the only workgroup that sees this cell
+        else if (vv > 0) plane_max(cell, vv);                            // segmented strip: merged like y-z
       }
     }
   }

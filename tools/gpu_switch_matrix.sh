@@ -27,3 +27,7 @@ run FVP_WINO_GENERIC=1
 run FVP_WINO_SHARED_COLS=0
 run FVP_WINO_SHARED_COLS=1
 run FVP_WINO_SHARED_COLS=2
+run FVP_TRI_OWNED=0
+run FVP_TRI_OWNED=1
+run FVP_TRI_OWNED=1 FVP_TRI_NY=1
+run FVP_TRI_OWNED=1 FVP_TRI_NY=3

@@ -36,6 +36,14 @@ class PoseResNet(ParamTree):
         assert list(r.NUM_DECONV_KERNELS) == [4] * int(r.NUM_DECONV_LAYERS), "only ConvTranspose(k4, s2, p1) deconvs"
         assert int(r.FINAL_CONV_KERNEL) == 1
         self.__dict__["deconv_filters"] = [int(f) for f in r.NUM_DECONV_FILTERS]
+        if len(self.deconv_filters) != int(r.NUM_DECONV_LAYERS):
+            raise capi.FvpError(f"NUM_DECONV_FILTERS {self.deconv_filters} does not list NUM_DECONV_LAYERS = "
+                                f"{int(r.NUM_DECONV_LAYERS)} layers")
+        for f in self.deconv_filters:
+            # a layer's output is the next layer's stored input: the conv kernels decode k = (tap, channel) by shifts
+            if f < 8 or f & (f - 1):
+                raise capi.FvpError(f"NUM_DECONV_FILTERS {self.deconv_filters}: the bf16 conv kernels take stored channel "
+                                    "counts that are powers of two >= 8")
         self.__dict__["deconv_bias"] = bool(r.DECONV_WITH_BIAS)
         self.__dict__["num_joints"] = int(cfg.DATASET.NUM_JOINTS)
         self.__dict__["device_name"] = str(cfg.DEVICE)

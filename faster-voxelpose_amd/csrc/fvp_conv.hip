@@ -954,6 +954,7 @@ static const int kNoK7 = int(env_size("FVP_CONV_NO_K7", 0));              // 7x7
 static const size_t kK7LdsPad = env_size("FVP_K7_LDS_KB", 0) * 1024;      // pad k_conv7's LDS request (fewer workgroups per CU)
 static const int kNoPoolFuse = int(env_size("FVP_CONV_NO_POOL_FUSE", 0)); // the max-pool behind a Winograd conv as its own launch
 static const int kNoHeadFuse = int(env_size("FVP_CONV_NO_HEAD_FUSE", 0)); // the 1x1 conv behind a paired transposed conv as its own launch
+static const int kNoSkipFuse = int(env_size("FVP_CONV_NO_SKIP_FUSE", 0)); // a res-block's 1x1 skip conv as its own launch
 static const int kNoReg = int(env_size("FVP_CONV_NO_REG", 0));            // 1x1 / transposed convs on k_conv_dma
 static const int kRegWgs = int(env_size("FVP_CONV_REG_WGS", 0));          // k_conv_reg: workgroups per CU
 static const int kNoKSplit = int(env_size("FVP_CONV_NO_KSPLIT", 0));      // no split-K form for the small-map 3x3 layers
@@ -1278,10 +1279,16 @@ static ConvArgs base_args(const FvpConvOp& op, const float* params, float* const
 }
 
 static int plan_and_launch(const FvpConvOp& op, const float* params, float* const* bufs, int planes, const uint8_t* plane_valid,
-                           int valid_div, hipStream_t s, float* pool_dst, const FvpConvOp* head) {
+                           int valid_div, hipStream_t s, float* pool_dst, const FvpConvOp* head, const FvpConvOp* skip = nullptr,
+                           bool plan_only = false) {
   ConvArgs a = base_args(op, params, bufs, planes, plane_valid, valid_div, pool_dst, head);
   if (double(planes) * std::max(op.cin, op.cout) * a.OH * a.OW >= 2147483648.0) return FVP_ELIMIT;
   const ConvForm form = conv_form(op, planes, pool_dst != nullptr, head != nullptr);
+  if (skip || plan_only) {                             // (eligibility: fused_skip())
+    if (form != ConvForm::Wino || !skip) return FVP_EINVAL;
+    a.skip_src = bufs[skip->src];
+    return wino_plan_and_launch(op, a, params, planes, s, skip, plan_only);
+  }
   if (op.kind == FVP_OP_CONVT2 && (form == ConvForm::Reg || form == ConvForm::TPair)) {
     a.wts = params + op.pair_off;                      // the paired copy: both column taps in one weight row,
     a.wrow = 2 * op.coutp;                             // grid.z = output row parity
@@ -1331,6 +1338,49 @@ static const FvpConvOp* fused_head(const FvpConvOp* ops, int nops, int i, int nb
   return only ? &nx : nullptr;
 }
 
+// A res-block's 1x1 skip conv, s = BN(conv1x1(x)), whose only reader is the block's second 3x3 conv, as its residual: that
+// conv computes s in its Winograd epilogue from x (k_conv_wino_skip, ConvArgs::skip_*) - the skip's launch, its write of s
+// and the read-back disappear, and the bits stay (the same ascending fmaf chain from zero, the same bn_affine).  Returns
+// the index of that conv, or -1: the skip is launched.  The rules:
+//   * the skip: 1x1, no ReLU, no residual of its own (an op does not say whether it has a BN: without one its packed scale
+//     and shift are 1 and 0, the same arithmetic); cin a multiple of 4 (one MFMA step = 4 channels) and <= 32;
+//   * cin <= 32 is the SHAPE rule of this fusion: at 64 -> 128 the skip's weights are 32 KB of LDS beside the 144 KB ring of
+//     the 128 -> 128 conv (the chunk would have to halve), its B operands 64 registers beside the 128 accumulators, and its
+//     128 MFMAs per unit are set against the shortest (17 us) of the three skip launches;
+//   * s is read exactly once before its buffer is written again: by a 3x3 conv of the same h, w and cout that takes the
+//     Winograd form, adds it before the ReLU (the fast order of the epilogue), and whose own input is another buffer (the
+//     block's first conv; a conv that reads x as its input too is not a res-block, and keeps the skip it reads);
+//   * x is still intact when that conv runs, and the conv writes neither x nor s;
+//   * the Winograd planner has room for the skip's weights in LDS beside the ring the conv has anyway (plan_only).
+static int fused_skip(const FvpConvOp* ops, int nops, int i, const float* params, float* const* bufs, int nbufs, int planes,
+                      const uint8_t* plane_valid, int valid_div) {
+  const FvpConvOp& sk = ops[i];
+  if (kNoSkipFuse || sk.kind != FVP_OP_CONV || sk.kh != 1 || sk.kw != 1 || sk.flags != 0 || sk.res >= 0) return -1;
+  if ((sk.cin != 16 && sk.cin != 32) || sk.cin != sk.cinp || sk.dst == sk.src) return -1;
+  int reader = -1;
+  for (int j = i + 1; j < nops; ++j) {
+    const FvpConvOp& o = ops[j];
+    const bool reads = o.src == sk.dst || (o.kind != FVP_OP_POOL2 && o.res == sk.dst);
+    if (reads && reader >= 0) return -1;
+    if (reads) reader = j;
+    if (o.dst == sk.dst) break;                        // (written again: later readers see another tensor)
+  }
+  if (reader < 0 || reader >= 64) return -1;
+  const FvpConvOp& r = ops[reader];
+  const int fast = FVP_EPI_RES | FVP_EPI_RELU;
+  if (r.kind != FVP_OP_CONV || r.kh != 3 || r.kw != 3 || r.res != sk.dst || r.src == sk.dst || r.src == sk.src ||
+      (r.flags & (fast | FVP_EPI_RES_AFTER_RELU)) != fast || r.h != sk.h || r.w != sk.w || r.cout != sk.cout ||
+      r.coutp != sk.coutp || r.dst == sk.src || r.dst == sk.dst || r.src < 0 || r.src >= nbufs || r.dst < 0 || r.dst >= nbufs)
+    return -1;
+  for (int j = i + 1; j < reader; ++j)
+    if (ops[j].dst == sk.src) return -1;
+  const int pool = fused_pool(ops, nops, reader, nbufs, planes);
+  if (plan_and_launch(r, params, bufs, planes, plane_valid, valid_div, nullptr, pool >= 0 ? bufs[ops[pool].dst] : nullptr, nullptr,
+                      &sk, /*plan_only=*/true))
+    return -1;
+  return reader;
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -1350,6 +1400,8 @@ extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* p
   }
   ProfScope stack_scope(FVP_K_CONV, as_stream(s), flops, nconv, prof_level() == 1);
   unsigned long long pooled = 0;                       // bit j: pool op j already done (by a conv's epilogue)
+  unsigned long long takes_skip = 0;                   // bit j: conv op j computes the skip conv skip_of[j] in its epilogue
+  int skip_of[64];
   for (int i = 0; i < nops; ++i) {
     const FvpConvOp& op = ops[i];
     FVP_REQUIRE(op.src >= 0 && op.src < nbufs && op.dst >= 0 && op.dst < nbufs && op.res < nbufs);
@@ -1364,11 +1416,18 @@ extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* p
                          valid_div > 0 ? valid_div : 1, op.cin);
       rc = launch_status();
     } else if (op.kind == FVP_OP_CONV || op.kind == FVP_OP_CONVT2) {
+      const int reader = fused_skip(ops, nops, i, params, bufs, nbufs, planes, plane_valid, valid_div);
+      if (reader >= 0) {                               // not launched: op `reader` computes it
+        takes_skip |= 1ull << reader;
+        skip_of[reader] = i;
+        continue;
+      }
       const int pool = fused_pool(ops, nops, i, nbufs, planes);
       if (pool >= 0) pooled |= 1ull << pool;
       const FvpConvOp* head = fused_head(ops, nops, i, nbufs, planes);
+      const FvpConvOp* skip = (i < 64 && ((takes_skip >> i) & 1)) ? &ops[skip_of[i]] : nullptr;
       rc = plan_and_launch(op, params, bufs, planes, plane_valid, valid_div, as_stream(s),
-                           pool >= 0 ? bufs[ops[pool].dst] : nullptr, head);
+                           pool >= 0 ? bufs[ops[pool].dst] : nullptr, head, skip);
       if (!rc && head) ++i;
     } else {
       rc = FVP_EINVAL;

@@ -72,6 +72,13 @@ struct ConvArgs {
   int epi_off;        // k_conv_dma: float offset of the BN vectors' copy in dynamic LDS (behind slots and epilogue scratch)
   int shcols;         // Winograd: 0 = every lane transforms its whole 4x4 patch; 1 / 2 = the tiles of a row share the first
                       // pass of the input transform, the neighbouring tile sits 1 (W = 32) / 2 (W = 16) lanes away
+  // Winograd with a fused res-block skip (k_conv_wino_skip / k_conv_wsc_skip): the residual is not read from `res` but
+  // computed in the epilogue, s = BN(conv1x1(skip_src)) - the 1x1 conv op in front of this one, which is then not launched
+  const float* skip_src;   // its input [planes][skip_cin][H][W]; nullptr: no fused skip
+  const float* skip_wts;   // its packed weights [skip_cin][coutp]
+  const float* skip_epi;   // its bias | scale | shift, each coutp
+  int skip_cin;            // its channels: 16 or 32 (4 or 8 MFMA steps: the kernels' template parameter SKIP)
+  int skip_off;            // float offset of its LDS copy (BN vectors, then the weights) in dynamic LDS
 };
 
 
@@ -134,7 +141,9 @@ ConvForm conv_form(const FvpConvOp& op, int planes, bool has_pool_dst, bool has_
 // shapes the Winograd kernel takes (a SHAPE rule, never the number of planes)
 bool wino_shape_ok(int h, int w, int cinp, int coutp);
 // plans and launches one 3x3 conv (ConvForm::Wino); `a` carries src / dst / res / epi / plane_valid / shape / flags / pool_dst
-int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s);
+// (`skip` / `plan_only`: the fused res-block skip and its look-ahead, see the definition)
+int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s,
+                         const FvpConvOp* skip = nullptr, bool plan_only = false);
 // state_dict weight [cout][cin][3][3] -> Winograd-domain copy at params + op.wino_off
 int wino_pack(const float* weight, const FvpConvOp& op, float* params, hipStream_t s);
 

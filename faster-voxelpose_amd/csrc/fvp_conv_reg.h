@@ -1,5 +1,7 @@
 // Register-direct conv for the layers with a SHORT reduction and no halo: the 1x1 skip / output convs and
 // ConvTranspose(k2, s2) of cnns_2d.py:40-72,74-112 (reference: lib/models/cnns_2d.py Res.skip_con :52-58, Upsample :62-72).
+// (Of the skips, only those the planner cannot fold into the block's second Winograd conv still come here - P2PNet's 64 -> 128
+// one, skips with a second reader: fused_skip() in fvp_conv.hip.  The fused form runs the chain below as 16x16x4 MFMAs.)
 //
 // Same implicit GEMM and the same v_mfma_f32_32x32x2_f32 chain as k_conv_dma (A = weights, B = pixels, channels in
 // ascending order from a zero accumulator: results are bit-identical to it), but nothing of the activations goes through

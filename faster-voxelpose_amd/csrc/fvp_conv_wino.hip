@@ -118,6 +118,7 @@ __global__ void __launch_bounds__(WC * WT * 64, (WC * WT == 16 ? 4 : 2)) k_conv_
   }
 #endif
   constexpr int SH = 0;
+  constexpr int SKIP = 0;
 #include "fvp_conv_wino_body.h"
 }
 
@@ -125,6 +126,34 @@ __global__ void __launch_bounds__(WC * WT * 64, (WC * WT == 16 ? 4 : 2)) k_conv_
 template <int WC, int WT, int CC, int NI, bool HAS_RES, bool RESW, int SH>
 __global__ void __launch_bounds__(WC * WT * 64, 2) k_conv_wsc(ConvArgs a) {
   constexpr int CW = 2;
+  constexpr int SKIP = 0;
+#include "fvp_conv_wino_body.h"
+}
+
+// The same two kernels with the res-block's 1x1 skip conv fused into the epilogue (SKIP in the body): the residual
+// s = BN(conv1x1(x)) is computed from x by 16x16x4 MFMAs instead of being read back (ConvArgs::skip_*).  Kernels of their
+// own names: the instances without a fused skip keep their code.
+// SKIP = the skip's MFMA steps: 4 (16 channels) or 8 (32).
+template <int WC, int WT, int CC, int NI, bool RESW, int SH, int SKIP>
+__global__ void k_conv_wsc_skip(ConvArgs a);
+
+template <int WC, int WT, int CC, int NI, bool RESW, int CW, int SKIP>
+__global__ void __launch_bounds__(WC * WT * 64, (WC * WT == 16 ? 4 : 2)) k_conv_wino_skip(ConvArgs a) {
+#if defined(HIPEMU)
+  if constexpr (CW == 2 && wino_shared_instance(WC, WT, CC, NI)) {
+    if (a.shcols == 1) return k_conv_wsc_skip<WC, WT, CC, NI, RESW, 1, SKIP>(a);
+    if (a.shcols == 2) return k_conv_wsc_skip<WC, WT, CC, NI, RESW, 2, SKIP>(a);
+  }
+#endif
+  constexpr int SH = 0;
+  constexpr bool HAS_RES = true;
+#include "fvp_conv_wino_body.h"
+}
+
+template <int WC, int WT, int CC, int NI, bool RESW, int SH, int SKIP>
+__global__ void __launch_bounds__(WC * WT * 64, 2) k_conv_wsc_skip(ConvArgs a) {
+  constexpr int CW = 2;
+  constexpr bool HAS_RES = true;
 #include "fvp_conv_wino_body.h"
 }
 
@@ -241,8 +270,39 @@ static int launch_wsc(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   hipLaunchKernelGGL(k, grid, dim3(WC * WT * 64), lds, s, a);
   return launch_status();
 }
+// the instance with the fused skip (ConvArgs::skip_src set): the own-patch kernel or, as in launch_wino3, its shared-column form
+template <int WC, int WT, int CC, int NI, bool RESW, int CW, int SKIP>
+static int launch_wino_skip(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+#if !defined(HIPEMU)
+  if constexpr (CW == 2 && wino_shared_instance(WC, WT, CC, NI)) {
+    if (a.shcols == 1 || a.shcols == 2) {
+      static LdsOptIn optin[2];
+      auto k = a.shcols == 1 ? &k_conv_wsc_skip<WC, WT, CC, NI, RESW, 1, SKIP> : &k_conv_wsc_skip<WC, WT, CC, NI, RESW, 2, SKIP>;
+      if (int e = lds_opt_in(optin[a.shcols - 1], reinterpret_cast<const void*>(k), 160 * 1024)) return e;
+      hipLaunchKernelGGL(k, grid, dim3(WC * WT * 64), lds, s, a);
+      return launch_status();
+    }
+  }
+  if (a.shcols) return FVP_EINVAL;
+#else
+  if (a.shcols == 1) hipemu::log_launch(reinterpret_cast<const void*>(&wino_shared_columns_form<1>));
+  if (a.shcols == 2) hipemu::log_launch(reinterpret_cast<const void*>(&wino_shared_columns_form<2>));
+#endif
+  static LdsOptIn optin;
+  auto k = &k_conv_wino_skip<WC, WT, CC, NI, RESW, CW, SKIP>;
+  if (int e = lds_opt_in(optin, reinterpret_cast<const void*>(k), 160 * 1024)) return e;
+  hipLaunchKernelGGL(k, grid, dim3(WC * WT * 64), lds, s, a);
+  return launch_status();
+}
 template <int WC, int WT, int CC, int NI, bool RES, bool RESW, int CW = 2>
 static int launch_wino3(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+  if (a.skip_src) {                                    // (the planner fuses a skip into two-wave-per-SIMD residual forms only)
+    if constexpr (RES && WC * WT != 16) {
+      if (a.skip_cin == 16) return launch_wino_skip<WC, WT, CC, NI, RESW, CW, 4>(a, grid, lds, s);
+      if (a.skip_cin == 32) return launch_wino_skip<WC, WT, CC, NI, RESW, CW, 8>(a, grid, lds, s);
+    }
+    return FVP_EINVAL;
+  }
 #if !defined(HIPEMU)
   if constexpr (CW == 2 && wino_shared_instance(WC, WT, CC, NI)) {
     if (a.shcols == 1) return launch_wsc<WC, WT, CC, NI, RES, RESW, 1>(a, grid, lds, s);
@@ -290,7 +350,12 @@ static int launch_wino(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s, 
   return launch_wino2<WC, WT, 4, false>(a, grid, lds, s);
 }
 
-int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s) {
+// `skip`: the res-block's 1x1 skip conv whose output is this conv's residual, to be computed in the epilogue from
+// a.skip_src (the caller's look-ahead, fused_skip() in fvp_conv.hip, found it); refused with FVP_ELIMIT where its LDS copy
+// does not fit beside the ring the conv has without it - the caller then launches the skip on its own.  `plan_only`: that
+// look-ahead's question - everything but the launch.
+int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s, const FvpConvOp* skip,
+                         bool plan_only) {
   int WC, WT, TN, TR;
   if (conv_form(op, planes, a.pool_dst != nullptr, a.w2 != nullptr) != ConvForm::Wino) return FVP_EINVAL;
   if (!wino_tiling(op.h, op.w, op.cinp, op.coutp, &WC, &WT, &TN, &TR, kWinoHalf == 1)) return FVP_EINVAL;
@@ -389,7 +454,25 @@ int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, i
   a.m_qpr = make_magic(op.w / 4 + 1);
   a.m_rpc = make_magic(TN * (a.TH + 2));
   a.m_thp = make_magic(a.TH + 2);
-  const size_t lds = 16 + 3 * slot + (resw ? resw_bytes : 0) + epi_bytes + flag_bytes;
+  size_t lds = 16 + 3 * slot + (resw ? resw_bytes : 0) + epi_bytes + flag_bytes;
+  double skip_flops = 0.0;
+  a.skip_src = skip ? a.skip_src : nullptr;
+  if (skip) {
+    // The fused skip's BN vectors and weights [skip_cin][coutp] behind the flags.  The ring (chunk size, DMA rounds, resident
+    // weights) stays what the conv has without the skip - planned against `budget` above - and the copy has to fit in what
+    // the CU has left: 160 KB for the one-per-CU workgroups, half of it for the two-per-CU ones.
+    if (w16 || !(a.flags & FVP_EPI_RES) || (skip->cin != 16 && skip->cin != 32) || skip->coutp != op.coutp)
+      return FVP_ELIMIT;
+    a.skip_off = int(lds / sizeof(float));
+    a.skip_cin = skip->cin;
+    a.skip_wts = params + skip->w_off;
+    a.skip_epi = params + skip->e_off;
+    const int sg = (skip->cin + 15) / 16;
+    lds += (size_t(3) * op.coutp + size_t(op.coutp) * 16 * sg) * sizeof(float);
+    if (lds > (WC * WT == 4 ? 80 : 160) * size_t(1024)) return FVP_ELIMIT;
+    skip_flops = 2.0 * skip->cin * skip->cout * double(op.h) * op.w * planes;
+  }
+  if (plan_only) return 0;
   a.ysplit = op.coutp / CBW;
   a.nunits = a.tiles_y * ceil_div(planes, TN) * a.ysplit;
   a.m_ys = make_magic(a.ysplit);
@@ -399,7 +482,7 @@ int wino_plan_and_launch(const FvpConvOp& op, ConvArgs a, const float* params, i
   static const int kBalanced = int(env_size("FVP_WINO_BALANCED", 0));
   const int slots = persistent_workgroups() * (WC * WT == 4 ? 2 : 1);
   dim3 grid(kBalanced ? ceil_div(a.nunits, ceil_div(a.nunits, slots)) : std::min(a.nunits, slots), 1, 1);
-  ProfScope ps(a.nunits < slots ? FVP_K_CONV_WINO_SMALL : FVP_K_CONV_WINO, s, 2.0 * op.cin * op.cout * 9.0 * op.h * op.w * planes, 1,
+  ProfScope ps(a.nunits < slots ? FVP_K_CONV_WINO_SMALL : FVP_K_CONV_WINO, s, 2.0 * op.cin * op.cout * 9.0 * op.h * op.w * planes + skip_flops, 1,
                prof_level() >= 2);
 #if FVP_DIAG
   if (w16) {

@@ -1,8 +1,10 @@
 // The body of the Winograd kernels of fvp_conv_wino.hip - k_conv_wino (SH = 0) and k_conv_wsc (SH = 1, 2) - included inside
 // each of the two kernel templates: NOT a header of its own.  The including function provides the kernel argument `a` and the
-// compile-time constants WC, WT, CC, NI, HAS_RES, RESW, CW and SH.  (One text instead of a shared __device__ function: behind
+// compile-time constants WC, WT, CC, NI, HAS_RES, RESW, CW, SH and SKIP.  (One text instead of a shared __device__ function: behind
 // a call boundary hipcc allocates the scalar registers of the own-patch instances differently - one of them spilled.)
   static_assert(SH == 0 || ((SH == 1 || SH == 2) && CW == 2), "shared columns: two-block waves");
+  constexpr bool kSkip = SKIP != 0;                  // SKIP = MFMA steps (4 channels each) of the fused 1x1 skip conv, 0: none
+  static_assert(SKIP == 0 || ((SKIP == 4 || SKIP == 8) && HAS_RES), "the fused skip is the residual: 16 or 32 channels");
   HIP_DYNAMIC_SHARED(float, smem)
   constexpr int NWV = WC * WT;                       // waves per workgroup: 8 / 16 (one workgroup per CU) or 4 (two per CU)
   constexpr int NT = NWV * 64;
@@ -31,6 +33,7 @@
   const bool dma = !(ablate & 1);
 
   // ---- LDS map (floats): [4 pad][3 ring slots][resident weights][bias | scale | shift][plane-group flags]
+  // (SKIP: [the skip's bias | scale | shift][the skip's weights] behind the flags, at a.skip_off)
   const int epi_off = 4 + 3 * BUF_SZ + (RESW ? a.cinp * CBW * 16 : 0);
   const unsigned char* const vflag = reinterpret_cast<const unsigned char*>(smem + epi_off + 3 * a.coutp);
 
@@ -270,6 +273,18 @@
     unsigned char* const f = const_cast<unsigned char*>(vflag);
     for (int i = t; i < a.nflags; i += NT) f[i] = a.plane_valid[i];
   }
+  // SKIP: the 1x1 skip conv's BN vectors and weights, once per workgroup.  Weights as A operands of its 16x16x4 MFMAs:
+  // Ws[cout][k4][g][j] = W[channel 4 (4 g + j) + k4][cout] - one ds_read_b128 gives a lane (cout, k4) four steps.
+  if constexpr (kSkip) {
+    float* const e = const_cast<float*>(smem) + a.skip_off;
+    for (int i = t; i < 3 * a.coutp; i += NT) e[i] = a.skip_epi[i];
+    float* const w = e + 3 * a.coutp;
+    constexpr int sg = SKIP / 4;
+    for (int i = t; i < a.skip_cin * a.coutp; i += NT) {
+      const int ci = i / a.coutp, co = i - ci * a.coutp;
+      w[((co * 4 + (ci & 3)) * sg + (ci >> 4)) * 4 + ((ci >> 2) & 3)] = a.skip_wts[i];
+    }
+  }
   if (dma) {
     stage_next(0, GlobalFlags{});
     stage_next(1, GlobalFlags{});
@@ -432,7 +447,23 @@
       const unsigned voff0 = tile_ok ? ((lco * unsigned(HW) + unsigned(y * W + x)) * 4u) & omask : kWinoOOB;
       const unsigned voffp = tile_ok ? (lco * unsigned(HW >> 2) + ppix) * 4u : kWinoOOB;
       fvp_f32x2 r0[CW][4], r1[CW][4];
-      if (HAS_RES && !(kDiag && (ablate & 16))) {      // (bit 16, diagnostics: no residual loads)
+      // SKIP: the residual is s = BN(conv1x1(x)), computed below from x instead of read back: the B operands of its MFMAs -
+      // x[4 s + k4] at the tile's 2x2 pixels, one 8-byte load per tile row and step - take the place of the residual loads
+      // (2 * skip_cin / 4 loads instead of 8 * CW; a masked tile reads zeros).
+      fvp_f32x2 xb[kSkip ? SKIP : 1][2];
+      if constexpr (kSkip) {
+        constexpr int scin = 4 * SKIP;
+        set_base(rs, ka->skip_src + size_t(plane0) * scin * HW);
+        const unsigned voffx = tile_ok ? unsigned((tn * scin + k4) * HW + y * W + x) * 4u : kWinoOOB;
+        unsigned so = 0;
+#pragma unroll
+        for (int s = 0; s < SKIP; ++s) {
+          xb[s][0] = asm_buffer_load_f32x2(voffx, rs, so);
+          xb[s][1] = asm_buffer_load_f32x2(voffx, rs, so + W4);
+          so += 4u * HW4;
+          FVP_OPAQUE(so);
+        }
+      } else if (HAS_RES && !(kDiag && (ablate & 16))) {      // (bit 16, diagnostics: no residual loads)
         unsigned so = 0;                               // scalar row offset (cb * 16 + r) * HW4, advanced as it is used: formed
 #pragma unroll                                         // up front, the 16 offsets of a lane's accesses are 16 more SGPRs
         for (int cb = 0; cb < CW; ++cb) {
@@ -481,6 +512,43 @@
       __builtin_amdgcn_sched_barrier(0);
       wait_vmcnt_imm<0>();
       __builtin_amdgcn_sched_barrier(0);
+      // SKIP: s[cout][pixel] = sum_ci Wskip[cout][ci] x[ci][pixel] as 16x16x4 MFMAs in the D layout of the accumulators (lane:
+      // tile l15, couts 4 k4 + r of the block), channels ascending from the constant-zero C - the fmaf chain k_conv_reg runs
+      // for the stand-alone skip, the same bits - then the skip's own BN.  One cout block at a time (four independent chains of
+      // skip_cin / 4 MFMAs, one per pixel of the tile): 16 result registers in flight, not 16 CW.
+      // The step count is the template parameter SKIP (4: 16 channels, 8: 32): with a run-time count the guarded steps cost
+      // 16 SGPRs of conditions and 21-46 spilled VGPRs in every two-block instance.
+      float sk[kSkip ? CW : 1][4][2][2];
+      if constexpr (kSkip) {
+        const float* const sk_s = smem + ka->skip_off;
+        constexpr int sg = SKIP / 4;
+        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int cb = 0; cb < CW; ++cb) {
+          const int cob = co0 + wc * (16 * CW) + cb * 16;
+          const float* const wrow = sk_s + 3 * coutp + ((cob + le15) * 4 + k4) * sg * 4;
+          f32x4 aw[kSkip ? sg : 1];
+#pragma unroll
+          for (int g = 0; g < sg; ++g) aw[g] = *reinterpret_cast<const f32x4*>(wrow + 4 * g);
+          f32x4 dd[2][2];
+#pragma unroll
+          for (int s = 0; s < SKIP; ++s)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              dd[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[s >> 2][s & 3], xb[s][i].x, s == 0 ? z : dd[i][0], 0, 0, 0);
+              dd[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[s >> 2][s & 3], xb[s][i].y, s == 0 ? z : dd[i][1], 0, 0, 0);
+            }
+          f32x4 bn[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) bn[i] = *reinterpret_cast<const f32x4*>(sk_s + i * coutp + cob + 4 * k4);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+              for (int e = 0; e < 2; ++e) sk[cb][r][i][e] = bn_affine(dd[i][e][r], bn[0][r], bn[1][r], bn[2][r]);
+        }
+      }
       // every P2PNet / CenterNet layer on this kernel is BN (+ residual) -> ReLU: that order gets its own copy of the loop (as
       // run-time flags the two selects per value were a quarter of the epilogue's instructions)
       auto finalize = [&](auto fastc) {
@@ -498,7 +566,14 @@
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float b = bn[0][r], sc = bn[1][r], sh = bn[2][r];
-            const float rr[2][2] = {{r0[cb][r].x, r0[cb][r].y}, {r1[cb][r].x, r1[cb][r].y}};
+            float rr[2][2];                          // the residual: loaded, or the fused skip's result
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                if constexpr (kSkip) rr[i][e] = sk[cb][r][i][e];
+                else rr[i][e] = i ? r1[cb][r][e] : r0[cb][r][e];
+              }
             float vv[2][2];
 #pragma unroll
             for (int i = 0; i < 2; ++i)

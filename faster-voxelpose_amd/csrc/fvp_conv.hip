@@ -38,6 +38,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kStageU = 4;   // independent 16-byte loads in flight per thread while staging
 constexpr int kStageS = 8;   // same for the 4-byte generic path
 
+// A masked plane (ConvArgs::plane_valid) is skipped: a tile of one plane returns before it stages anything, a tile of
+// several planes (TN > 1) computes them all and predicates its stores with this.
+template <class AP>
+__device__ __forceinline__ bool plane_live(AP a, int plane) {
+  return !a->plane_valid || a->TN == 1 || a->plane_valid[plane / a->valid_div];
+}
+
 // ---------------------------------------------------------------------------------------------
 // Shared epilogue: bias, BN scale/shift, residual, ReLU; coalesced NCHW stores.  Residual values
 // are fetched with unconditional (address-clamped) loads, 16 per accumulator tile, before any
@@ -60,7 +67,7 @@ __device__ __forceinline__ void conv_epilogue(KArgsPtr a, const float* epi, f32x
     const int n = qc / (a->TH * a->TW), r2 = qc - n * (a->TH * a->TW);
     const int ty = r2 / a->TW, tx = r2 - ty * a->TW;
     const int plane = plane0 + n, y = y0 + ty, x = x0 + tx;
-    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H && x < a->W;
+    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H && x < a->W && plane_live(a, plane);
     const size_t opix = pix_ok ? size_t(y * a->osy + dy) * a->OW + (x * a->osx + dx) : 0;
     const size_t pbase = pix_ok ? size_t(plane) * a->cout : 0;
 #pragma unroll
@@ -290,7 +297,7 @@ __device__ __forceinline__ void conv_epilogue_pair(KArgsPtr a, const float* epi,
     const int n = fdiv(qc, a->m_thw), r2 = qc - n * (a->TH * Wq);
     const int ty = fdiv(r2, a->m_w), tx = r2 - ty * Wq;
     const int plane = plane0 + n, y = y0 + ty;
-    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H;
+    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H && plane_live(a, plane);
     const unsigned pix = pix_ok ? unsigned(y * a->W + 2 * tx) : 0u;
     const unsigned pbase = pix_ok ? unsigned(plane) * a->cout : 0u;
     float2 rv[8];
@@ -350,7 +357,7 @@ __device__ __forceinline__ void conv_epilogue_tpair(AP a, const float* epi, f32x
     const int n = fdiv(qc, a->m_thw), r2 = qc - n * (a->TH * a->W);
     const int ty = fdiv(r2, a->m_w), tx = r2 - ty * a->W;
     const int plane = plane0 + n, y = y0 + ty;
-    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H;
+    const bool pix_ok = q < tile_px && plane < a->planes && y < a->H && plane_live(a, plane);
     const unsigned pix = pix_ok ? unsigned((2 * y + dy) * a->OW + 2 * tx) : 0u;
     const unsigned pbase = pix_ok ? unsigned(plane) * a->cout : 0u;
 #pragma unroll
@@ -480,7 +487,7 @@ __device__ __forceinline__ void conv_epilogue_wide(KArgsPtr a, const float* epi,
         const int n = fdiv(qc, a->m_thw), r2 = qc - n * (a->TH * a->TW);
         const int ty = fdiv(r2, a->m_w), tx = r2 - ty * a->TW;
         const int plane = plane0 + n, y = y0 + ty;
-        ok[j] = q < tile_px && plane < a->planes && y < a->H && co[j] < a->cout;
+        ok[j] = q < tile_px && plane < a->planes && y < a->H && co[j] < a->cout && plane_live(a, plane);
         off[j] = ok[j] ? unsigned((plane * a->cout + co[j]) * HW + y * a->W + tx) : 0u;
         if (HAS_RES) rv[j] = *reinterpret_cast<const float4*>(a->res + off[j]);
       }

@@ -323,6 +323,7 @@ extern "C" int fvp_conv_stack_run_fused_1d(const FvpConvOp* ops, int nops, const
     const int Lo = op.kind == FVP_OP_CONVT2 ? 2 * op.w : (op.kind == FVP_OP_POOL2 ? op.w / 2 : op.w);
     FVP_LIMIT(Lo <= 24);
     if (op.kind == FVP_OP_CONV) FVP_LIMIT(op.kh == 1 && (op.kw == 1 || op.kw == 3 || op.kw == 7));
+    if (op.kind == FVP_OP_POOL2) FVP_REQUIRE(op.w % 2 == 0);   // as fvp_conv_stack_run: no odd-length pool
     FVP_LIMIT(op.e_off % 4 == 0 && op.coutp % 4 == 0);   // the epilogue vectors are staged by 16-byte LDS-DMA items
     chan[op.src] = op.cin;
     len[op.src] = op.w;
@@ -332,12 +333,18 @@ extern "C" int fvp_conv_stack_run_fused_1d(const FvpConvOp* ops, int nops, const
     if (first[op.dst] < 0) first[op.dst] = i;
     lastuse[op.src] = i;
     if (op.res >= 0) lastuse[op.res] = i;
+    if (lastuse[op.dst] < i) lastuse[op.dst] = i;      // a dst is live while its op runs, read later or not (see below)
     if (op.dst + 1 > nbufs) nbufs = op.dst + 1;
     if (op.src + 1 > nbufs) nbufs = op.src + 1;
     if (op.kind != FVP_OP_POOL2)
       flops += 2.0 * op.cin * op.cout * (op.kind == FVP_OP_CONVT2 ? 2.0 : double(op.kw)) * op.w * planes;
     a.ops[i] = op;
   }
+  // the kernel's pool step writes LDS only: a stack that ends in a pool would leave `out` untouched
+  FVP_REQUIRE(ops[nops - 1].kind != FVP_OP_POOL2);
+  // Every dst is live while its op runs (lastuse >= its own op, above), whether anyone reads it later or not: the last op's
+  // epilogue stores to `out`, a dead middle op's result is dropped, but a transposed conv's slot-clearing step still writes
+  // the LDS slots of dst, which must not lie on the residual (or the input) of that op.
   // ---- LDS placement: first-fit over live ranges [def, last use]
   int off[kMaxBufs], size[kMaxBufs];
   int total = 0;

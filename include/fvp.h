@@ -313,8 +313,14 @@ int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* params, floa
 
 /* The same interpreter for a 1-D stack (H = 1, W <= 24, cout <= 128: C2CNet) fused into ONE
  * kernel, one workgroup per plane, activations resident in LDS.  in = [planes][cin][W] (buffer
- * ops[0].src), out = [planes][cout][W'] of the last op.  Results are identical to
- * fvp_conv_stack_run (same accumulation order). */
+ * ops[0].src), out = [planes][cout][W'] of the last op.  Deterministic; equal to fvp_conv_stack_run
+ * up to rounding (each op's reduction is split into four K slices added in a fixed order).
+ * The last op must be a conv or a transposed conv (its epilogue is what stores to `out`; its
+ * residual, if any, is kept like any other op's): a stack that ends in a max-pool is refused with
+ * FVP_EINVAL, and so is a pool of an odd length, exactly as fvp_conv_stack_run refuses it.
+ * FVP_ELIMIT: nops > 32, more than 40 buffers, W or W' > 24, coutp > 128, a conv that is not
+ * 1 x {1, 3, 7}, a stack whose activations and weight ring exceed 160 KB of LDS.  Nothing is
+ * written when an error is returned. */
 int fvp_conv_stack_run_fused_1d(const FvpConvOp* ops, int nops, const float* params, const float* in,
                                 float* out, int planes, fvp_stream_t s);
 

@@ -244,7 +244,7 @@ POISON_GUARD = 4096            # floats of guard region before and after every p
 
 
 def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_valid=None, valid_div=1, poison=False, eps=1e-5,
-                          info=None):
+                          info=None, allow_rc=()):
     """Run a hand-made ``netspec.StackSpec`` (finalized) through fvp_pack_conv + fvp_conv_stack_run.
     ``weights``: {key + '.weight' / '.bias': tensor}, and for a conv with a BN key {bn + '.weight' / '.bias' /
     '.running_mean' / '.running_var'}; ``x``: [planes, C, H, W].  Returns every activation buffer.
@@ -254,12 +254,23 @@ def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_vali
     every guard is bit-identical (else the stack wrote out of bounds) and that every output element of a valid plane
     (plane_valid[n // valid_div] != 0) is finite (a NaN there was read from memory the zero padding should have masked,
     or is an element nobody wrote).  On the CPU emulation (tests/hipemu) the guards are also read fences: check() asserts
-    that no emulated buffer load read them, even a value the kernel then discarded."""
+    that no emulated buffer load read them, even a value the kernel then discarded.  check(unwritten=ids): those buffers
+    must still hold POISON_BITS everywhere (a map a fused epilogue never stores, every buffer after a refusal) instead of
+    finite values.  ``allow_rc``: error codes of fvp_conv_stack_run that do not raise (info['rc'] receives the code)."""
     import ctypes as C
 
     from faster_voxelpose_amd import _capi as capi
     blob = torch.zeros(max(spec.nparams, 4), device=device)
     s = stream
+    pack_custom_conv_stack(lib, device, spec, weights, blob, s, eps)
+    return _run_packed_conv_stack(lib, device, spec, blob, x, s, plane_valid, valid_div, poison, info, allow_rc)
+
+
+def pack_custom_conv_stack(lib, device, spec, weights, blob, s=None, eps=1e-5):
+    """fvp_pack_conv for every conv of a finalized spec into ``blob`` (see run_custom_conv_stack)."""
+    import ctypes as C
+
+    from faster_voxelpose_amd import _capi as capi
     keep = []
     for key, bn, transposed, oi in spec.param_keys:
         w = weights[key + ".weight"].to(device).contiguous()
@@ -273,6 +284,13 @@ def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_vali
         capi.check(lib, lib.fvp_pack_conv(C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), *bnp, eps,
                                           1 if transposed else 0, C.byref(spec.op_array[oi]), C.c_void_p(blob.data_ptr()), s),
                    "fvp_pack_conv")
+    return blob
+
+
+def _run_packed_conv_stack(lib, device, spec, blob, x, s, plane_valid, valid_div, poison, info, allow_rc):
+    import ctypes as C
+
+    from faster_voxelpose_amd import _capi as capi
     planes = x.shape[0]
     shapes = [(planes,) + tuple(b) for b in spec.bufs]
     if not poison:
@@ -299,8 +317,12 @@ def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_vali
             lib.hipemu_fence(C.c_void_p(f.data_ptr() + 4 * (G + n)), 4 * G)
     arr = (C.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
     pv = None if plane_valid is None else plane_valid.to(device=device, dtype=torch.uint8).contiguous()
-    capi.check(lib, lib.fvp_conv_stack_run(spec.op_array, len(spec.ops), C.c_void_p(blob.data_ptr()), arr, len(bufs), planes,
-                                           None if pv is None else C.c_void_p(pv.data_ptr()), valid_div, s), "fvp_conv_stack_run")
+    rc = lib.fvp_conv_stack_run(spec.op_array, len(spec.ops), C.c_void_p(blob.data_ptr()), arr, len(bufs), planes,
+                                None if pv is None else C.c_void_p(pv.data_ptr()), valid_div, s)
+    if info is not None:
+        info["rc"] = rc
+    if rc not in allow_rc:
+        capi.check(lib, rc, "fvp_conv_stack_run")
     reads = 0
     if fence:
         reads = int(lib.hipemu_fenced_reads())
@@ -310,7 +332,7 @@ def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_vali
     if not poison:
         return bufs
 
-    def check():
+    def check(unwritten=()):
         # (on the device: the buffers of a 240-plane layer are gigabytes)
         valid = torch.ones(planes, dtype=torch.bool)
         if plane_valid is not None:
@@ -322,7 +344,10 @@ def run_custom_conv_stack(lib, device, spec, weights, x, stream=None, plane_vali
             n = bits.numel() - 2 * G
             bad = int((bits[:G] != POISON_BITS).sum()) + int((bits[G + n:] != POISON_BITS).sum())
             assert bad == 0, f"buffer {i}: {bad} guard words changed (out-of-bounds write)"
-            if i > 0:
+            if i in unwritten:
+                nw = int((bits[G:G + n] != POISON_BITS).sum())
+                assert nw == 0, f"buffer {i}: {nw} elements written (it must stay untouched)"
+            elif i > 0:
                 nf = int((~torch.isfinite(bufs[i][valid])).sum())
                 assert nf == 0, f"buffer {i}: {nf} non-finite elements in valid planes (unwritten, or read unmasked memory)"
     return bufs, check
@@ -555,3 +580,249 @@ def reg_stack(seed=0, fused_head=True, head_cout=15):
         o_s32 = F.conv2d(d, W["s32.weight"], W["s32.bias"]) + x
         return dict(u64=o_u64, head=o_head, s32=o_s32)
     return spec, w, ref, dict(u64=u64, head=head, s32=s32)
+
+
+# ---- non-Winograd conv forms, layer by layer (tests/conv_form_cases.py, tests/conv1d_fused_cases.py) ----------------------
+# A-priori error bound of one direct conv / transposed conv op against its float64 evaluation, per output element:
+#
+#     |y - y64| <= gamma * ( |s| * (conv(|x|, |w|) + |b|) + |t| + |r| ),   gamma = (cinp * taps + c) * eps32
+#
+# (b: bias, s / t: the packed BN scale / shift, r: the residual; ReLU and max-pool are 1-Lipschitz).  Every direct form
+# (k_conv, k_conv_dma and its pixel-pair / paired-transposed forms, k_conv7, k_conv_reg) sums an output's cinp * taps products
+# in ONE chain of fused multiply-adds on the fp32 matrix cores (v_mfma_f32_32x32x2_f32 / 16x16x4: one rounding per product
+# added; padded channels and the pixel-pair form's eighth tap column are zero products, which round nothing).  The standard
+# bound of an n-term fp32 chain is n * u relative to the sum of magnitudes, u = eps32 / 2; eps32 is used, which also covers
+# a matrix core that rounds the products of one instruction separately.  taps = kh * kw, and 1 for ConvTranspose(k2,s2):
+# kernel = stride, so each output pixel sees exactly one tap.  c counts the roundings outside the chain, from the code:
+#   * the epilogue, bn_affine() in csrc/fvp_common.h: acc + bias (1), fmaf(., scale, shift) (1), and + residual (1):
+#     CONV_EPI_ROUNDINGS = 3;
+#   * split K: k_conv_dma<..., KS> (four waves) and k_conv1d_fused (kKS = 4 slices) add four partial chains in the fixed
+#     order 0, 1, 2, 3: three more adds, CONV_SPLIT_ROUNDINGS = 3 (pass split=True).
+# A fused chain of ops without stored intermediates (the 1x1 head in a transposed conv's epilogue, the whole 1-D stack in
+# k_conv1d_fused) is bounded by propagation (conv_chain_reference): an op's input error e enters its output as
+# |s| * conv(e, |w|) (+ the residual's own error), max-pooled by a pool; the magnitudes are taken at |x64| + e.
+CONV_EPI_ROUNDINGS = 3
+CONV_SPLIT_ROUNDINGS = 3
+
+
+def conv_gamma(op, split=False):
+    """gamma of the bound above for a finalized op (capi.FvpConvOp or the dict of spec.ops with cinp)."""
+    from faster_voxelpose_amd import _capi as capi
+    taps = 1 if op.kind == capi.OP_CONVT2 else op.kh * op.kw
+    return (op.cinp * taps + CONV_EPI_ROUNDINGS + (CONV_SPLIT_ROUNDINGS if split else 0)) * EPS32
+
+
+def conv_layer(kind, cin, cout, hw, *, k=1, dim=2, relu=True, res=False, res_after=False, bn=False, pool=False, head=None, tail=None,
+               seed=0):
+    """One op of the conv interpreter as a finalized ``netspec.StackSpec`` (generalises wino_layer):
+      kind 'conv': a k x k (dim 2) / 1 x k (dim 1) conv cin -> cout on hw (+ BN of both signs, residual before / after the
+                   ReLU - the input when cin == cout, else a 1x1 projection of it earlier in the stack -, ``pool``: a max-pool
+                   behind it);
+      kind 'up':   ConvTranspose(k2,s2) cin -> cout from hw to 2 x hw with its skip (ReLU, then + skip).  The stack's input is
+                   the skip [cout, 2h, 2w]; the transposed conv reads its max-pool (through a 1x1 conv cout -> cin when
+                   cin != cout); ``head``: a 1x1 conv cout -> head behind it (P2PNet's output layer);
+      kind 'pool': a 2x2 / 1x2 max-pool of the input.
+    ``tail``: a 1x1 conv to that many channels behind the op (behind the pool where there is one; 'head' for kind 'up'), so
+    that the op is a middle op whose result is observed through it.
+    hw: (h, w), h = 1 when dim == 1.  Returns (spec, weights, ids): ids = {'op' (index of the op under test), 'out', 'pool',
+    'head' (buffer ids or None), 'head_op'}."""
+    from faster_voxelpose_amd import netspec
+    h, w_ = (hw, hw) if isinstance(hw, int) else hw
+    assert dim == 2 or h == 1
+    g = torch.Generator().manual_seed(seed)
+    wt = {}
+
+    def params(key, ci, co, kk, transposed=False):
+        ks = (kk,) * dim
+        wt[key + ".weight"] = torch.randn(((ci, co) if transposed else (co, ci)) + ks, generator=g) / (ci * (1 if transposed else kk ** dim)) ** 0.5
+        wt[key + ".bias"] = torch.randn(co, generator=g) * 0.1
+
+    def bn_params(key, co):
+        # scales of both signs and per-cout shifts that differ from one 32-cout block to the next (as wino_layer)
+        blk = (torch.arange(co) // 32).float()
+        wt[key + ".weight"] = (0.5 + torch.rand(co, generator=g)) * torch.where(torch.rand(co, generator=g) < 0.3, -1.0, 1.0) * (1 + 0.25 * blk)
+        wt[key + ".bias"] = torch.randn(co, generator=g) * 0.2 + 0.1 * blk
+        wt[key + ".running_mean"] = torch.randn(co, generator=g) * 0.1 - 0.05 * blk
+        wt[key + ".running_var"] = 0.5 + torch.rand(co, generator=g) + 0.1 * blk
+
+    ids = dict(pool=None, head=None, head_op=None)
+    if kind == "conv":
+        spec = netspec.StackSpec(dim, cin, (h, w_))
+        spec._conv_entries("c", cin, cout, k)
+        params("c", cin, cout, k)
+        if bn:
+            spec._bn_entries("n", cout)
+            bn_params("n", cout)
+        rid = None
+        if res:
+            rid = 0
+            if cin != cout:
+                spec._conv_entries("p", cin, cout, 1)
+                params("p", cin, cout, 1)
+                rid = spec.conv("p", None, 0, cout, 1, relu=False)
+        o = spec.conv("c", "n" if bn else None, 0, cout, k, relu=relu, res=rid, res_after_relu=res_after)
+        ids["op"] = len(spec.ops) - 1
+        if pool:
+            ids["pool"] = spec.pool(o)
+    elif kind == "up":
+        spec = netspec.StackSpec(dim, cout, (2 * h if dim == 2 else 1, 2 * w_))
+        src = spec.pool(0)
+        if cin != cout:
+            spec._conv_entries("q", cout, cin, 1)
+            params("q", cout, cin, 1)
+            src = spec.conv("q", None, src, cin, 1, relu=False)
+        spec._conv_entries("u", cin, cout, 2, transposed=True)
+        params("u", cin, cout, 2, transposed=True)
+        if bn:
+            spec._bn_entries("n", cout)
+            bn_params("n", cout)
+        o = spec.up("u", "n" if bn else None, src, cout, 0)
+        ids["op"] = len(spec.ops) - 1
+        if head is not None:
+            spec._conv_entries("h", cout, head, 1)
+            params("h", cout, head, 1)
+            ids["head"] = spec.conv("h", None, o, head, 1, relu=False)
+            ids["head_op"] = len(spec.ops) - 1
+    else:
+        assert kind == "pool"
+        spec = netspec.StackSpec(dim, cin, (h, w_))
+        o = spec.pool(0)
+        ids["op"] = 0
+    ids["out"] = o
+    ids["tail"] = None
+    if tail is not None:
+        last = ids["pool"] if ids["pool"] is not None else o
+        spec._conv_entries("t", spec.bufs[last][0], tail, 1)
+        params("t", spec.bufs[last][0], tail, 1)
+        ids["tail"] = spec.conv("t", None, last, tail, 1, relu=False)
+    spec.outputs["out"] = o
+    spec.finalize()
+    return spec, wt, ids
+
+
+def conv_packed_epi(spec, blob, i):
+    """(bias, scale, shift) of op i as packed in the parameter blob (float32 values as the kernel reads them, float64 dtype)."""
+    o = spec.op_array[i]
+    e = blob[o.e_off:o.e_off + 3 * o.coutp].cpu().double()
+    return e[:o.cout], e[o.coutp:o.coutp + o.cout], e[2 * o.coutp:2 * o.coutp + o.cout]
+
+
+def _conv_lin(spec, weights, i, x, absw=False):
+    """float64 conv / transposed conv of op i without bias: x [P, cin, H, W] -> [P, cout, H', W']."""
+    import torch.nn.functional as F
+
+    from faster_voxelpose_amd import _capi as capi
+    o = spec.op_array[i]
+    key = [k for k, _, _, oi in spec.param_keys if oi == i][0]
+    w = weights[key + ".weight"].double()
+    if absw:
+        w = w.abs()
+    if o.kind == capi.OP_CONVT2:
+        w = w.reshape(o.cin, o.cout, o.kh, o.kw)
+        return F.conv_transpose2d(x, w, None, stride=(o.kh, o.kw))
+    w = w.reshape(o.cout, o.cin, o.kh, o.kw)
+    return F.conv2d(x, w, None, padding=(o.kh // 2, o.kw // 2))
+
+
+def conv_op_reference(spec, weights, blob, i, x, r=None, xerr=None, rerr=None):
+    """float64 evaluation of op i of a finalized spec on the input x (and residual r) and the magnitude term of the bound
+    above: (y, mag, lin) in float64; mag is to be multiplied by conv_gamma().  A pool op returns (max-pool, None, None).
+    With xerr / rerr (error bounds of x / r, chains of fused ops) the magnitudes are taken at |x| + xerr and ``lin`` is the
+    propagated input error |s| * conv(xerr, |w|) + rerr (else None)."""
+    import torch.nn.functional as F
+
+    from faster_voxelpose_amd import _capi as capi
+    o = spec.op_array[i]
+    x = x.double()
+    if o.kind == capi.OP_POOL2:
+        kk = (2, 2) if o.h > 1 else (1, 2)
+        return F.max_pool2d(x, kk), None, (None if xerr is None else F.max_pool2d(xerr, kk))
+    b, s, t = (v.view(1, -1, 1, 1) for v in conv_packed_epi(spec, blob, i))
+    y = (_conv_lin(spec, weights, i, x) + b) * s + t
+    xa = x.abs() if xerr is None else x.abs() + xerr
+    mag = s.abs() * (_conv_lin(spec, weights, i, xa, absw=True) + b.abs()) + t.abs()
+    lin = None if xerr is None else s.abs() * _conv_lin(spec, weights, i, xerr, absw=True)
+    relu, after = bool(o.flags & capi.EPI_RELU), bool(o.flags & capi.EPI_RES_AFTER_RELU)
+    if r is not None:
+        r = r.double()
+        mag = mag + r.abs() + (0.0 if rerr is None else rerr)
+        if lin is not None and rerr is not None:
+            lin = lin + rerr
+    if r is not None and not after:
+        y = y + r
+    if relu:
+        y = torch.relu(y)
+    if r is not None and after:
+        y = y + r
+    return y, mag, lin
+
+
+def conv_chain_reference(spec, weights, blob, x, split=False, known=None, only=None):
+    """float64 evaluation of the ops of a finalized spec (``only``: those op indices, in order) with the propagated error
+    bound of every buffer they write.  ``known``: {buffer id: tensor} of buffers taken as exact inputs (default: the stack
+    input x as buffer 0).  Returns ({buffer id: y64}, {buffer id: error bound})."""
+    from faster_voxelpose_amd import _capi as capi
+    val = {0: x.double()} if known is None else {b: v.double() for b, v in known.items()}
+    err = {b: torch.zeros_like(v) for b, v in val.items()}
+    for i in (range(len(spec.ops)) if only is None else only):
+        o = spec.op_array[i]
+        r = val[o.res] if (o.kind != capi.OP_POOL2 and o.res >= 0) else None
+        y, mag, lin = conv_op_reference(spec, weights, blob, i, val[o.src], r, xerr=err[o.src], rerr=None if r is None else err[o.res])
+        val[o.dst] = y
+        err[o.dst] = lin if mag is None else conv_gamma(o, split) * mag + lin
+    return val, err
+
+
+def conv_ratio(y, y64, bound):
+    """max |y - y64| / bound; > 1 = the bound is violated.  NaN counts as a violation."""
+    e = (y.double() - y64).abs()
+    if not torch.isfinite(e).all():
+        return float("inf")
+    return float((e / (bound + 1e-300)).max()) if e.numel() else 0.0
+
+
+def conv_check_packed_epi(spec, weights, blob, eps=1e-5):
+    """The epilogue vectors fvp_pack_conv wrote against the values folded from ``weights`` in float64: the bias bit for bit,
+    scale = gamma / sqrt(var + eps) and shift = beta - mean * scale to 4 ulp of their terms (1 and 0 without a BN).  The
+    references below read bias | scale | shift from the blob, as the kernels do: this keeps them independent of the packing."""
+    for key, bn, _, oi in spec.param_keys:
+        b, s, t = conv_packed_epi(spec, blob, oi)
+        assert torch.equal(b, weights[key + ".bias"].double()), f"{key}: packed bias differs"
+        if bn is None:
+            assert bool((s == 1).all()) and bool((t == 0).all()), f"{key}: packed scale / shift without a BN are not 1 / 0"
+            continue
+        g, beta, mean, var = (weights[bn + k].double() for k in (".weight", ".bias", ".running_mean", ".running_var"))
+        s64 = g / torch.sqrt(var + eps)
+        assert bool(((s - s64).abs() <= 4 * EPS32 * s64.abs()).all()), f"{bn}: packed scale differs"
+        assert bool(((t - (beta - mean * s64)).abs() <= 4 * EPS32 * (beta.abs() + (mean * s64).abs())).all()), f"{bn}: packed shift differs"
+
+
+def conv_stack_ratio(spec, weights, blob, bufs, sel=slice(None), split=False, unstored=()):
+    """Worst error / bound over every op of a stack that ran with stored intermediates ``bufs`` (planes ``sel``): each op
+    against the float64 evaluation of its own stored inputs (conv_gamma, or WINO_K for an op with a Winograd weight copy); a
+    max-pool must be exact (else inf).  ``unstored``: buffers a fused epilogue never wrote - their producer is skipped and
+    their readers are checked through the propagated chain bound from the producer's inputs."""
+    from faster_voxelpose_amd import _capi as capi
+    conv_check_packed_epi(spec, weights, blob)
+    cpu = [b[sel].cpu() for b in bufs]
+    ops = spec.op_array
+    worst = 0.0
+    for i in range(len(spec.ops)):
+        o = ops[i]
+        if o.dst in unstored:
+            continue
+        if o.src in unstored:
+            j = max(k for k in range(i) if ops[k].dst == o.src)
+            known = {b: cpu[b] for b in (ops[j].src, ops[j].res, o.res) if b >= 0 and b not in unstored}
+            val, err = conv_chain_reference(spec, weights, blob, None, split=split, known=known, only=(j, i))
+            worst = max(worst, conv_ratio(cpu[o.dst], val[o.dst], err[o.dst]))
+            continue
+        r = cpu[o.res] if (o.kind != capi.OP_POOL2 and o.res >= 0) else None
+        y, mag, _ = conv_op_reference(spec, weights, blob, i, cpu[o.src], r)
+        if mag is None:
+            if not torch.equal(cpu[o.dst].contiguous().view(torch.int32), y.float().contiguous().view(torch.int32)):
+                return float("inf")
+        else:
+            gamma = WINO_K * EPS32 if o.wino_off > 0 else conv_gamma(o, split)
+            worst = max(worst, conv_ratio(cpu[o.dst], y, gamma * mag))
+    return worst

@@ -161,8 +161,11 @@ static void run_block(Worker* w, dim3 bid, dim3 grid, dim3 block) {
   }
 }
 
+static std::atomic<size_t> last_shmem{0};
+
 void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body) {
   const int n = block.x * block.y * block.z;
+  last_shmem = shmem;
   if (n % 64 != 0 || n > 1024 || shmem > kDynSmem) {
     fprintf(stderr, "hipemu: unsupported launch (block %d threads, %zu B dynamic LDS)\n", n, shmem);
     abort();
@@ -238,6 +241,8 @@ extern "C" void hipemu_fences_clear() {
   hipemu::nfences = 0;
   hipemu::fenced_reads = 0;
 }
+// dynamic LDS bytes of the last launch (tests pin a kernel's LDS footprint with it)
+extern "C" size_t hipemu_last_shmem() { return hipemu::last_shmem.load(); }
 extern "C" long hipemu_fenced_reads() { return hipemu::fenced_reads.load(); }
 
 // the log since the last reset (valid until the next launch or reset: the caller copies it)

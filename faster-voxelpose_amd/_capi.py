@@ -39,6 +39,20 @@ class FvpGeom(C.Structure):
                 ("V", C.c_int32), ("J", C.c_int32), ("JP", C.c_int32)]
 
 
+def make_geom(ds, rt6, J):
+    """The one builder of ``FvpGeom``: ``ds`` = ``cfg.DATASET``, ``rt6`` the six floats of the 2x3 resize transform; V
+    is left 0 for the caller to set per call."""
+    g = FvpGeom()
+    g.clamp_max = float(max(ds.ORI_IMAGE_SIZE[0], ds.ORI_IMAGE_SIZE[1]))
+    for i in range(6):
+        g.rt[i] = float(rt6[i])
+    g.W, g.H = int(ds.HEATMAP_SIZE[0]), int(ds.HEATMAP_SIZE[1])
+    g.hm_w, g.hm_h = float(g.W), float(g.H)
+    g.img_w, g.img_h = float(ds.IMAGE_SIZE[0]), float(ds.IMAGE_SIZE[1])
+    g.V, g.J, g.JP = 0, int(J), (int(J) + 3) // 4 * 4
+    return g
+
+
 class FvpConvOp(C.Structure):
     _fields_ = [("kind", C.c_int32), ("src", C.c_int32), ("dst", C.c_int32), ("res", C.c_int32),
                 ("cin", C.c_int32), ("cout", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),

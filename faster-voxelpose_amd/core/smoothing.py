@@ -10,16 +10,12 @@ association (the tracker still matches against the raw last pose), re-identifica
 
 No arithmetic happens here and nothing synchronises with the host: PyTorch is used for device memory and streams only.
 """
-import ctypes as C
-
 import torch
 
 from .. import _capi as capi
+from .._args import (SequenceRows, device_matches, frame_rows, load_lib, require_gpu, stream_ptr, tensor_arg)
+from .._args import ptr as _ptr
 from .tracking import PoseTracker
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class PoseSmoother:
@@ -44,7 +40,6 @@ class PoseSmoother:
 
     def __init__(self, tracker_or_shape, rate_hz=30.0, min_cutoff=1.0, beta=0.005, d_cutoff=1.0, conf_min=0.0, damp=0.8,
                  max_age=None, device=None, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
         self.tracker = tracker_or_shape if isinstance(tracker_or_shape, PoseTracker) else None
         if self.tracker is not None:
             tr = self.tracker
@@ -55,16 +50,13 @@ class PoseSmoother:
                 _lib = tr.lib
         else:
             N, J, T, nseq = tracker_or_shape
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         self.N, self.J, self.T, self.nseq = int(N), int(J), int(T), int(nseq)
         self.max_age = 15 if max_age is None else int(max_age)
         self.rate_hz, self.min_cutoff, self.beta = float(rate_hz), float(min_cutoff), float(beta)
         self.d_cutoff, self.conf_min, self.damp = float(d_cutoff), float(conf_min), float(damp)
         self.device = torch.device("cuda" if device is None else device)
-        if not self._injected and self.device.type != "cuda":
-            raise capi.FvpError(f"device={str(self.device)!r}: the smoother runs on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
+        require_gpu("the smoother", self.device, self._injected)
         if self.N < 1 or self.J < 1 or self.nseq < 1 or self.T < self.N or self.max_age < 0:
             raise capi.FvpError(f"PoseSmoother needs N, J, nseq >= 1, T >= N and max_age >= 0 (N = {self.N}, J = {self.J}, "
                                 f"nseq = {self.nseq}, T = {self.T}, max_age = {self.max_age})")
@@ -81,35 +73,16 @@ class PoseSmoother:
         self.flt_vel = torch.zeros((self.nseq, self.T, self.J, 3), device=dev)
         self.flt_id = torch.full((self.nseq, self.T), -1, dtype=torch.int32, device=dev)
         self.flt_age = torch.zeros((self.nseq, self.T), dtype=torch.int32, device=dev)
-        # without a tracker to share the numbering with: sequence name -> state row in order of first appearance
-        self.seq_ids = self.tracker.seq_ids if self.tracker is not None else {}
-        self._frame_sets = {}
+        # the tracker's numbering when built from one; else sequence name -> state row in order of first appearance
+        self._rows = SequenceRows(limit=self.nseq)
+        self.seq_ids = self.tracker.seq_ids if self.tracker is not None else self._rows.ids
 
     # ---------------------------------------------------------------------------------------------
-    def _stream(self):
-        if self.device.type == "cuda":
-            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
     def frame_sets(self, seqs):
         """[B] int32 device tensor of state rows for a list of sequence names: the tracker's numbering when built from one."""
         if self.tracker is not None:
             return self.tracker.frame_sets(seqs)
-        seqs = tuple(seqs)
-        for s in seqs:
-            if s not in self.seq_ids:
-                if len(self.seq_ids) >= self.nseq:
-                    raise capi.FvpError(f"sequence {s!r} is one more than the nseq = {self.nseq} this smoother was built for "
-                                        f"(known: {list(self.seq_ids)})")
-                self.seq_ids[s] = len(self.seq_ids)
-        if seqs not in self._frame_sets:
-            if len(self._frame_sets) >= 256:            # bounded, as in the engine
-                self._frame_sets.pop(next(iter(self._frame_sets)))
-            self._frame_sets[seqs] = torch.tensor([self.seq_ids[s] for s in seqs], dtype=torch.int32, device=self.device)
-        return self._frame_sets[seqs]
-
-    def _same_device(self, t):
-        return t.device == self.device or (self.device.index is None and t.device.type == self.device.type)
+        return self._rows.rows(seqs, self.device)
 
     def update(self, fused_poses, ids, slots, joint_conf=None, meta=None, sequences=None):
         """One batch ``fused_poses [B,N,J,5]`` with the ``ids [B,N]`` and ``slots [B,N]`` ``PoseTracker.update`` returned
@@ -122,38 +95,14 @@ class PoseSmoother:
 
         ``joint_conf [B,N,J]`` (``last_evidence[1]``): joints below ``conf_min`` are predicted; None: every finite joint is
         measured.  ``sequences`` / ``meta`` as for ``PoseTracker.update``."""
-        t = fused_poses
-        if t.dtype != torch.float32:
-            raise capi.FvpError(f"fused_poses must be float32, got {t.dtype}")
-        if not self._same_device(t):
+        t = tensor_arg("fused_poses", fused_poses, torch.float32, ("B", self.N, self.J, 5))
+        if not device_matches(t.device, self.device):
             raise capi.FvpError(f"fused_poses lives on {t.device}, the smoother was built for {self.device}")
-        if t.dim() != 4 or tuple(t.shape[1:]) != (self.N, self.J, 5) or not t.is_contiguous():
-            raise capi.FvpError(f"fused_poses must be contiguous [B,{self.N},{self.J},5], got {tuple(t.shape)}")
         B = t.shape[0]
         for name, x in (("ids", ids), ("slots", slots)):
-            if not torch.is_tensor(x) or x.dtype != torch.int32 or x.device != t.device or tuple(x.shape) != (B, self.N) \
-                    or not x.is_contiguous():
-                raise capi.FvpError(f"{name} must be a contiguous int32 tensor [{B},{self.N}] on {t.device} (what "
-                                    f"PoseTracker.update returned for this batch)")
-        if joint_conf is not None:
-            c = joint_conf
-            if c.dtype != torch.float32 or c.device != t.device or tuple(c.shape) != (B, self.N, self.J) \
-                    or not c.is_contiguous():
-                raise capi.FvpError(f"joint_conf must be a contiguous float32 tensor [{B},{self.N},{self.J}] on {t.device}, "
-                                    f"got {c.dtype} {tuple(c.shape)} on {c.device}")
-        if sequences is None and meta is not None:
-            sequences = meta["seq"]
-        if sequences is None:
-            fs = None
-        elif torch.is_tensor(sequences):
-            fs = sequences
-            if fs.dtype != torch.int32 or fs.device != t.device or tuple(fs.shape) != (B,) or not fs.is_contiguous():
-                raise capi.FvpError(f"sequences must be a contiguous int32 tensor [{B}] on {t.device}, got {fs.dtype} "
-                                    f"{tuple(fs.shape)} on {fs.device}")
-        else:
-            if len(sequences) != B:
-                raise capi.FvpError(f"{len(sequences)} sequence names for {B} frames")
-            fs = self.frame_sets(sequences)
+            tensor_arg(name, x, torch.int32, (B, self.N), t.device, hint="what PoseTracker.update returned for this batch")
+        tensor_arg("joint_conf", joint_conf, torch.float32, (B, self.N, self.J), t.device, optional=True)
+        fs = frame_rows(self.frame_sets, sequences, meta, B, t.device)
         smooth = torch.empty_like(t)
         track_poses = torch.empty((B, self.T, self.J, 4), device=self.device)
         track_state = torch.empty((B, self.T, 2), dtype=torch.int32, device=self.device)
@@ -163,7 +112,7 @@ class PoseSmoother:
                                        _ptr(self.flt_vel), _ptr(self.flt_id), _ptr(self.flt_age), _ptr(smooth),
                                        _ptr(track_poses), _ptr(track_state), B, self.N, self.J, self.nseq, self.T,
                                        self.rate_hz, self.min_cutoff, self.beta, self.d_cutoff, self.conf_min, self.damp,
-                                       self.max_age, self._stream())
+                                       self.max_age, stream_ptr(self.device))
         capi.check(self.lib, rc, "fvp_track_smooth")
         return smooth, track_poses, track_state
 

@@ -10,15 +10,11 @@ predictions), re-identification after ``max_age``, Hungarian (optimal) assignmen
 
 No arithmetic happens here and nothing synchronises with the host: PyTorch is used for device memory and streams only.
 """
-import ctypes as C
-
 import torch
 
 from .. import _capi as capi
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from .._args import (SequenceRows, device_matches, frame_rows, load_lib, require_gpu, stream_ptr, tensor_arg)
+from .._args import ptr as _ptr
 
 
 class PoseTracker:
@@ -36,9 +32,7 @@ class PoseTracker:
     ``trk_age [nseq,T]``, ``next_id [nseq]``."""
 
     def __init__(self, cfg_or_N_J, nseq=1, max_tracks=None, gate_mm=500.0, max_age=15, device=None, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         if isinstance(cfg_or_N_J, (tuple, list)):
             N, J = cfg_or_N_J
         else:
@@ -48,9 +42,7 @@ class PoseTracker:
         self.T = 2 * self.N if max_tracks is None else int(max_tracks)
         self.gate_mm, self.max_age = float(gate_mm), int(max_age)
         self.device = torch.device("cuda" if device is None else device)
-        if not self._injected and self.device.type != "cuda":
-            raise capi.FvpError(f"device={str(self.device)!r}: the tracker runs on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
+        require_gpu("the tracker", self.device, self._injected)
         if self.N < 1 or self.J < 1 or self.nseq < 1 or self.T < self.N or self.max_age < 0:
             raise capi.FvpError(f"PoseTracker needs N, J, nseq >= 1, max_tracks >= N and max_age >= 0 (N = {self.N}, "
                                 f"J = {self.J}, nseq = {self.nseq}, max_tracks = {self.T}, max_age = {self.max_age})")
@@ -63,31 +55,13 @@ class PoseTracker:
         self.trk_id = torch.full((self.nseq, self.T), -1, dtype=torch.int32, device=dev)
         self.trk_age = torch.zeros((self.nseq, self.T), dtype=torch.int32, device=dev)
         self.next_id = torch.zeros((self.nseq,), dtype=torch.int32, device=dev)
-        # sequence name -> row of the state, in order of first appearance: the rule of HotPath.frame_sets, so a tracker fed
-        # the meta['seq'] lists the engine is fed numbers the sequences as the engine does
-        self.seq_ids = {}
-        self._frame_sets = {}
+        self._rows = SequenceRows(limit=self.nseq)
+        self.seq_ids = self._rows.ids                  # sequence name -> row of the state, in order of first appearance
 
     # ---------------------------------------------------------------------------------------------
-    def _stream(self):
-        if self.device.type == "cuda":
-            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
-
     def frame_sets(self, seqs):
         """[B] int32 device tensor of state rows for a list of sequence names (uploaded once per distinct list)."""
-        seqs = tuple(seqs)
-        for s in seqs:
-            if s not in self.seq_ids:
-                if len(self.seq_ids) >= self.nseq:
-                    raise capi.FvpError(f"sequence {s!r} is one more than the nseq = {self.nseq} this tracker was built for "
-                                        f"(known: {list(self.seq_ids)})")
-                self.seq_ids[s] = len(self.seq_ids)
-        if seqs not in self._frame_sets:
-            if len(self._frame_sets) >= 256:            # bounded, as in the engine
-                self._frame_sets.pop(next(iter(self._frame_sets)))
-            self._frame_sets[seqs] = torch.tensor([self.seq_ids[s] for s in seqs], dtype=torch.int32, device=self.device)
-        return self._frame_sets[seqs]
+        return self._rows.rows(seqs, self.device)
 
     def update(self, fused_poses, meta=None, sequences=None):
         """One batch ``fused_poses [B,N,J,5]`` (the forward's first output, or any poses in that layout), frames in time
@@ -99,27 +73,11 @@ class PoseTracker:
         ``engine.frame_sets()`` returns: the forward passes its own), or a list of B sequence names - else
         ``meta['seq']``, else sequence 0 for every frame.  A row outside [0, nseq) belongs to no sequence: the frame comes
         back all -1 and changes nothing."""
-        t = fused_poses
-        if t.dtype != torch.float32:
-            raise capi.FvpError(f"fused_poses must be float32, got {t.dtype}")
-        if t.device != self.device and not (self.device.index is None and t.device.type == self.device.type):
+        t = tensor_arg("fused_poses", fused_poses, torch.float32, ("B", self.N, self.J, 5))
+        if not device_matches(t.device, self.device):
             raise capi.FvpError(f"fused_poses lives on {t.device}, the tracker was built for {self.device}")
-        if t.dim() != 4 or tuple(t.shape[1:]) != (self.N, self.J, 5) or not t.is_contiguous():
-            raise capi.FvpError(f"fused_poses must be contiguous [B,{self.N},{self.J},5], got {tuple(t.shape)}")
         B = t.shape[0]
-        if sequences is None and meta is not None:
-            sequences = meta["seq"]
-        if sequences is None:
-            fs = None
-        elif torch.is_tensor(sequences):
-            fs = sequences
-            if fs.dtype != torch.int32 or fs.device != t.device or tuple(fs.shape) != (B,) or not fs.is_contiguous():
-                raise capi.FvpError(f"sequences must be a contiguous int32 tensor [{B}] on {t.device}, got {fs.dtype} "
-                                    f"{tuple(fs.shape)} on {fs.device}")
-        else:
-            if len(sequences) != B:
-                raise capi.FvpError(f"{len(sequences)} sequence names for {B} frames")
-            fs = self.frame_sets(sequences)
+        fs = frame_rows(self.frame_sets, sequences, meta, B, t.device)
         ids = torch.empty((B, self.N), dtype=torch.int32, device=self.device)
         slots = torch.empty((B, self.N), dtype=torch.int32, device=self.device)
         costs = torch.empty((B, self.N), device=self.device)
@@ -127,7 +85,7 @@ class PoseTracker:
             return ids, slots, costs
         rc = self.lib.fvp_track_update(_ptr(t), _ptr(fs), _ptr(self.trk_pose), _ptr(self.trk_id), _ptr(self.trk_age),
                                        _ptr(self.next_id), _ptr(ids), _ptr(slots), _ptr(costs), B, self.N, self.J,
-                                       self.nseq, self.T, self.gate_mm, self.max_age, self._stream())
+                                       self.nseq, self.T, self.gate_mm, self.max_age, stream_ptr(self.device))
         capi.check(self.lib, rc, "fvp_track_update")
         return ids, slots, costs
 

@@ -15,11 +15,13 @@ between: ``Nv12Frames`` describes the two planes (pitch and frame stride are the
 pixel with the integer formula of ``include/fvp.h``.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 
 from .. import _capi as capi
+from .._args import f3, load_lib, ptr, require_gpu, stream_ptr, tensor_arg
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)        # run/validate.py:44-45
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -58,29 +60,25 @@ class _InverseCache:
 _inverse = _InverseCache()
 
 
-def _f3(v):
-    v = [float(x) for x in v]
-    assert len(v) == 3
-    return (C.c_float * 3)(*v)
-
-
 def launch(lib, frames, resize_transform, image_size, swap_rb, mean, std, nhwc8, nchw, general=False):
     """One ``fvp_ingest_frames`` call on the current stream.  ``frames`` uint8 ``[N,Hs,Ws,3]`` contiguous;
     ``image_size`` = (W, H) like ``cfg.DATASET.IMAGE_SIZE``; ``nhwc8`` / ``nchw``: output tensors or None."""
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise capi.FvpError(f"frames must be uint8 [N,Hs,Ws,3], got {frames.dtype} {tuple(frames.shape)}")
-    if not frames.is_contiguous():
-        raise capi.FvpError("frames must be contiguous (HWC)")
-    N, Hs, Ws, _ = frames.shape
+    N, Hs, Ws, _ = tensor_arg("frames", frames, torch.uint8, ("N", "Hs", "Ws", 3), hint="HWC").shape
     W, H = int(image_size[0]), int(image_size[1])
     inv = _inverse.get(resize_transform)
     flags = (capi.INGEST_SWAP_RB if swap_rb else 0) | (capi.INGEST_GENERAL if general else 0)
-    stream = C.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream) if frames.is_cuda else None
-    rc = lib.fvp_ingest_frames(C.c_void_p(frames.data_ptr()), N, Hs, Ws, (C.c_float * 6)(*[float(v) for v in inv]),
-                               _f3(mean), _f3(std), H, W, flags,
-                               C.c_void_p(nhwc8.data_ptr()) if nhwc8 is not None else None,
-                               C.c_void_p(nchw.data_ptr()) if nchw is not None else None, stream)
+    rc = lib.fvp_ingest_frames(ptr(frames), N, Hs, Ws, (C.c_float * 6)(*[float(v) for v in inv]), f3(mean), f3(std), H, W,
+                               flags, ptr(nhwc8), ptr(nchw), stream_ptr(frames.device))
     capi.check(lib, rc, "fvp_ingest_frames")
+
+
+def _out_arg(out, shape, device):
+    """The fp32 output of an ingest call: a new tensor, or the caller's - held to its element count, not to a shape."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or out.numel() != math.prod(shape) or not out.is_contiguous() or out.device != device:
+        raise capi.FvpError(f"out must be a contiguous float32 tensor of {shape} on {device}")
+    return out
 
 
 def ingest_frames(frames, resize_transform, image_size, swap_rb=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
@@ -90,18 +88,12 @@ def ingest_frames(frames, resize_transform, image_size, swap_rb=True, mean=IMAGE
     array - the object the model gets; ``image_size`` = (W, H).  ``swap_rb`` turns BGR frames (cv2.imread) into the RGB
     order the ImageNet constants are in.  Returns fp32 ``[N,3,H,W]`` (``[B,V,3,H,W]``): the tensor the reference's
     loader hands to the backbone."""
-    if _lib is None and not frames.is_cuda:
-        raise capi.FvpError("ingest_frames runs on the GPU only (no CPU fallback)")
-    lib = _lib if _lib is not None else capi.load()
+    require_gpu("ingest_frames", frames.device, _lib is not None)
+    lib, _ = load_lib(_lib)
     lead = tuple(frames.shape[:-3])
     flat = frames.reshape(-1, *frames.shape[-3:]) if frames.dim() == 5 else frames
     W, H = int(image_size[0]), int(image_size[1])
-    shape = (flat.shape[0], 3, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
-    elif out.dtype != torch.float32 or out.numel() != flat.shape[0] * 3 * H * W or not out.is_contiguous() \
-            or out.device != frames.device:
-        raise capi.FvpError(f"out must be a contiguous float32 tensor of {shape} on {frames.device}")
+    out = _out_arg(out, (flat.shape[0], 3, H, W), frames.device)
     launch(lib, flat, resize_transform, (W, H), swap_rb, mean, std, None, out)
     return out.view(*lead, 3, H, W)
 
@@ -193,12 +185,10 @@ def launch_nv12(lib, frames, resize_transform, image_size, mean, std, nhwc8, nch
         raise capi.FvpError(f"frames must be Nv12Frames, got {type(frames).__name__}")
     W, H = int(image_size[0]), int(image_size[1])
     inv = _inverse.get(resize_transform)
-    stream = C.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream) if frames.is_cuda else None
-    rc = lib.fvp_ingest_nv12(C.c_void_p(frames.y.data_ptr()), C.c_void_p(frames.uv.data_ptr()), frames.N, frames.Hs,
-                             frames.Ws, frames.y_pitch, frames.uv_pitch, frames.y_frame_stride, frames.uv_frame_stride,
-                             frames.standard, (C.c_float * 6)(*[float(v) for v in inv]), _f3(mean), _f3(std), H, W,
-                             C.c_void_p(nhwc8.data_ptr()) if nhwc8 is not None else None,
-                             C.c_void_p(nchw.data_ptr()) if nchw is not None else None, stream)
+    rc = lib.fvp_ingest_nv12(ptr(frames.y), ptr(frames.uv), frames.N, frames.Hs, frames.Ws, frames.y_pitch, frames.uv_pitch,
+                             frames.y_frame_stride, frames.uv_frame_stride, frames.standard,
+                             (C.c_float * 6)(*[float(v) for v in inv]), f3(mean), f3(std), H, W, ptr(nhwc8), ptr(nchw),
+                             stream_ptr(frames.device))
     capi.check(lib, rc, "fvp_ingest_nv12")
 
 
@@ -208,15 +198,9 @@ def ingest_nv12(frames, resize_transform, image_size, mean=IMAGENET_MEAN, std=IM
     swap_rb=False)`` returns for the frames converted to RGB with the integer formula of ``include/fvp.h``."""
     if not isinstance(frames, Nv12Frames):
         raise capi.FvpError(f"frames must be Nv12Frames, got {type(frames).__name__}")
-    if _lib is None and not frames.is_cuda:
-        raise capi.FvpError("ingest_nv12 runs on the GPU only (no CPU fallback)")
-    lib = _lib if _lib is not None else capi.load()
+    require_gpu("ingest_nv12", frames.device, _lib is not None)
+    lib, _ = load_lib(_lib)
     W, H = int(image_size[0]), int(image_size[1])
-    shape = (frames.N, 3, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
-    elif out.dtype != torch.float32 or out.numel() != frames.N * 3 * H * W or not out.is_contiguous() \
-            or out.device != frames.device:
-        raise capi.FvpError(f"out must be a contiguous float32 tensor of {shape} on {frames.device}")
+    out = _out_arg(out, (frames.N, 3, H, W), frames.device)
     launch_nv12(lib, frames, resize_transform, (W, H), mean, std, None, out)
     return out.view(*frames.lead, 3, H, W)

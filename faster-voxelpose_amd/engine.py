@@ -12,12 +12,10 @@ import torch
 
 from . import _capi as capi
 from . import netspec
+from ._args import ptr as _ptr
+from ._args import stream_ptr
 
 BN_EPS = 1e-5
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class SharedGeometry:
@@ -140,9 +138,7 @@ class HotPath:
 
     # ---------------------------------------------------------------------------------------------
     def stream(self):
-        if self.device.type == "cuda":
-            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return None
+        return stream_ptr(self.device)
 
     def _call(self, name, *args):
         capi.check(self.lib, getattr(self.lib, name)(*args), name)
@@ -162,17 +158,7 @@ class HotPath:
         if self._geom is None or key is None or key != self._geom_key:
             rt = np.asarray(resize_transform.detach().cpu() if isinstance(resize_transform, torch.Tensor)
                             else resize_transform, dtype=np.float32).reshape(6)
-            ds = self.cfg.DATASET
-            g = capi.FvpGeom()
-            g.clamp_max = float(max(ds.ORI_IMAGE_SIZE[0], ds.ORI_IMAGE_SIZE[1]))
-            for i in range(6):
-                g.rt[i] = float(rt[i])
-            g.hm_w, g.hm_h = float(self.W), float(self.H)
-            g.img_w, g.img_h = float(ds.IMAGE_SIZE[0]), float(ds.IMAGE_SIZE[1])
-            g.W, g.H = self.W, self.H
-            g.V = 0
-            g.J, g.JP = self.J, self.JP
-            self._geom, self._geom_key = g, key
+            self._geom, self._geom_key = capi.make_geom(self.cfg.DATASET, rt, self.J), key
         return self._geom
 
     @staticmethod

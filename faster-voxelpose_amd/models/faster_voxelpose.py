@@ -7,29 +7,13 @@ cameras=None, resize_transform=None)`` returns
 
 Beyond the reference: ``model.evidence = True`` makes ``forward`` also leave ``model.last_evidence = (views [B,V,N,J,4],
 joint_conf [B,N,J])`` - every fused joint reprojected into every camera image with its heatmap support there, and the
-per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``).  ``model.tracker = PoseTracker(cfg)``
-(core/tracking.py) makes ``forward`` also leave ``model.last_tracks = (ids [B,N], slots [B,N], costs [B,N])`` - one
-identity per person across the frames of a camera sequence, one more launch, no host synchronisation.
-``model.smoother = PoseSmoother(model.tracker)`` (core/smoothing.py) makes it also leave ``model.last_smooth = (smooth
-[B,N,J,5], track_poses [B,T,J,4], track_state [B,T,2])`` - the One-Euro-filtered pose of every track, slot-stable, unsupported
-joints and dropped-out tracks bridged by prediction; one more launch behind the tracker's.
-``model.overlay = PoseOverlay(cfg)`` (utils/overlay.py; needs ``evidence`` and ``uint8`` camera frames as ``views``) makes it
-also draw the skeletons into the caller's frames, in place, coloured by track id when a tracker is set; built with
-``nv12=True`` it also draws into ``Nv12Frames`` views, in the surface itself.
-``model.crops = PersonCrops(cfg)`` (utils/crops.py; needs ``evidence`` and ``uint8`` or ``Nv12Frames`` camera frames as
-``views``) makes it also leave ``model.last_crops = (patches [B,V,N,3,h,w], rois [B,V,N,4], count [B,V,N], score [B,V,N])`` -
-a normalised, fixed-size image patch of every person in every view, cut out before the overlay draws; two more launches.
-``model.visibility = JointVisibility(cfg)`` (utils/visibility.py; needs ``evidence``) makes it also leave
-``model.last_visibility = (occluder [B,V,N,J], vis_conf [B,N,J], vis_count [B,N,J])`` - which cameras see each joint past the
-other people's bodies, and the joint's confidence over those views only; one more launch behind the evidence's.
-``model.triangulator = JointTriangulator(cfg)`` (utils/triangulate.py) makes it also leave ``model.last_triangulation =
-(tri_poses [B,N,J,5], tri_count [B,N,J], tri_stats [B,N,J,2], obs [B,V,N,J,4], view_state [B,V,N,J], cam_resid [B,V], cam_count
-[B,V])`` - every joint triangulated from the heat-map peaks of the views, its distance from the fused joint, the reprojection
-residual per view and per camera; one or two more launches behind the evidence's and the visibility's.
-``model.recalibrator = CameraRefiner(cfg)`` (utils/recalibrate.py; needs ``triangulator``) makes it also accumulate every
-forward's observations against the engine's camera tables in ``model.recalibrator.acc`` - one more launch behind the
-triangulation's; ``model.recalibrator.solve(model.engine.geo.cams)`` then gives the corrected camera records.
+per-joint confidence the model itself defines (``FasterVoxelPoseNet.joint_evidence``) - and a stage object assigned to one of
+the attributes of ``STAGES`` makes it also run that stage behind its own poses.  Every stage is static-shape and free of host
+synchronisation like the rest of the forward, so under ``GraphedForward`` / ``GraphedPipeline`` its launches are part of the
+captured graph and its ``last_*`` holds static tensors, overwritten by the next replay; the returned tuple is the same with
+and without it, and unset (None) the forward issues exactly the launches it issues without the feature.
 """
+import collections
 import time
 
 import torch
@@ -40,6 +24,72 @@ from ..dataset.images import Nv12Frames, ingest_frames, ingest_nv12
 from ..engine import HotPath
 from .human_detection_net import HumanDetectionNet
 from .joint_localization_net import JointLocalizationNet
+
+# One row per optional stage of the forward, in the order in which PipelinedForward refuses them.  ``attr``: the model
+# attribute that holds the stage object; ``last``: the attribute the forward leaves its result in; ``needs``: what else has
+# to be set, each with the reason the error message gives - "evidence" (model.evidence = True), "tracker", "triangulator",
+# "frames" (camera frames as ``views``: uint8 [B,V,Hs,Ws,3] or Nv12Frames); ``about``: what the forward does with it;
+# ``recipe``: what to do instead on the consumer stream of a pipeline, which takes no stage.  The calls themselves are
+# FasterVoxelPoseNet._run_stages.
+Stage = collections.namedtuple("Stage", "attr last needs about recipe")
+STAGES = (
+    Stage("tracker", "last_tracks", {},
+          "a core.tracking.PoseTracker: tracker.update() on the fused poses (one more launch, frames in batch order, the "
+          "frames' sequence rows are the engine's own) leaves (ids [B,N], slots [B,N], costs [B,N]): one identity per person "
+          "across the frames of a camera sequence.  The track state lives in device memory and carries from call to call, "
+          "and from replay to replay of a captured graph.",
+          "call tracker.update(outputs[0], meta) on the consumer stream in submit order"),
+    Stage("smoother", "last_smooth", {"tracker": "filters the tracks of model.tracker"},
+          "a core.smoothing.PoseSmoother: smoother.update() behind the tracker's, on last_tracks and the stages' joint_conf "
+          "(one more launch), leaves (smooth [B,N,J,5], track_poses [B,T,J,4], track_state [B,T,2]): the One-Euro-filtered "
+          "pose of every track, slot-stable, unsupported joints and dropped-out tracks bridged by prediction.",
+          "call smoother.update(outputs[0], ids, slots, meta=meta) behind tracker.update on the consumer stream in submit "
+          "order"),
+    Stage("overlay", "last_overlay_views", {"evidence": "draws the pixels of model.last_evidence",
+                                            "frames": "draws into the camera frames"},
+          "a utils.overlay.PoseOverlay: draws the skeletons into the caller's frames, in place, behind tracker, smoother and "
+          "crops (one more launch) - from last_evidence[0], or, with a smoother, from one more joint_evidence() of "
+          "last_smooth[0] kept in last_overlay_views (issued once for crops and overlay) - coloured by last_tracks[0], gated "
+          "by the stages' joint_conf.  Nv12Frames views are drawn on, in the surface itself, only by an overlay built with "
+          "nv12=True: the surface is the decoder's own memory.",
+          "call overlay.draw(frames, views, ids) on the consumer stream"),
+    Stage("crops", "last_crops", {"evidence": "cuts around the pixels of model.last_evidence",
+                                  "frames": "cuts the patches out of the camera frames"},
+          "a utils.crops.PersonCrops: cuts a normalised, fixed-size patch per (frame, view, person) out of the caller's "
+          "frames before the overlay paints them (two more launches) - boxes around the pixels the overlay would draw, "
+          "last_tracks[0] as ids, the stages' joint_conf - and leaves (patches [B,V,N,3,h,w], rois [B,V,N,4], count [B,V,N], "
+          "score [B,V,N]).",
+          "call crops(frames, views, ids) on the consumer stream, with views from model.joint_evidence(outputs[0], ...)[0], "
+          "before any overlay.draw"),
+    Stage("visibility", "last_visibility", {"evidence": "judges the pixels of model.last_evidence"},
+          "a utils.visibility.JointVisibility: tests every fused joint's line of sight to every camera against the other "
+          "people's bodies, right behind the evidence launch (one more launch, on last_evidence[0] and the engine's camera "
+          "tables), and leaves (occluder [B,V,N,J], vis_conf [B,N,J], vis_count [B,N,J]).  Built with feeds_conf=True (the "
+          "default), vis_conf takes the place of last_evidence[1] as the joint_conf of smoother, overlay and crops.",
+          "call visibility(outputs[0], cameras, meta, views=views) on the consumer stream, with views from "
+          "model.joint_evidence(outputs[0], ...)[0]"),
+    Stage("recalibrator", None, {"triangulator": "reads the triangulation's obs and view_state"},
+          "a utils.recalibrate.CameraRefiner: adds this batch's observations to recalibrator.acc, one launch right behind "
+          "the triangulation's, on last_triangulation and the engine's camera tables; model.recalibrator_points: 'fused' "
+          "(the forward's joints) or 'tri' (the triangulated ones) as the 3-D points.  Solving and adopting stay with the "
+          "caller (recalibrator.solve(model.engine.geo.cams), camera_dicts): the engine's tables are never swapped here.",
+          "call recalibrator.accumulate(outputs[0], obs, view_state, cams, frame_set) behind the triangulator on the "
+          "consumer stream"),
+    Stage("triangulator", "last_triangulation", {},
+          "a utils.triangulate.JointTriangulator: triangulates every fused joint from the heat-map peaks of the views, "
+          "behind the evidence and visibility launches (one or two more launches, on the staging copy of this forward and "
+          "the engine's camera tables, last_visibility[0] as the occluder table), and leaves (tri_poses [B,N,J,5], tri_count "
+          "[B,N,J], tri_stats [B,N,J,2], obs [B,V,N,J,4], view_state [B,V,N,J], cam_resid [B,V], cam_count [B,V]).  The poses "
+          "handed to tracker, smoother, overlay and crops stay the fused ones.",
+          "call triangulator(outputs[0], cameras, meta, heat_cl) on the consumer stream, with heat_cl from "
+          "model.engine.heat_cl(outputs[3], geom)"),
+)
+_STAGE = {s.attr: s for s in STAGES}
+_CHECKED_FIRST = ("smoother", "visibility", "overlay", "crops")    # forward() checks their needs before any launch, in this order
+_REMEDY = {"tracker": "set model.tracker (a PoseTracker) too", "evidence": "set model.evidence = True too",
+           "triangulator": "set model.triangulator = JointTriangulator(cfg) as well",
+           "frames": "pass them as views, uint8 [B,V,Hs,Ws,3] or Nv12Frames (float images and input_heatmaps alone leave "
+                     "nothing to work on; an overlay takes Nv12Frames only when built with nv12=True)"}
 
 
 class FasterVoxelPoseNet(nn.Module):
@@ -60,53 +110,10 @@ class FasterVoxelPoseNet(nn.Module):
         # `last_evidence`; the returned tuple is the same either way
         self.evidence = False
         self.last_evidence = None
-        # a core.tracking.PoseTracker: forward() also calls tracker.update() on its own fused_poses (one more launch on the
-        # current stream, frames in batch order) and keeps (ids, slots, costs) in `last_tracks`; the returned tuple is the
-        # same either way.  None: the forward issues exactly the launches it issues without the feature.
-        self.tracker = None
-        self.last_tracks = None
-        # a core.smoothing.PoseSmoother (needs `tracker`): forward() also calls smoother.update() behind the tracker's, on
-        # `last_tracks` - with `last_evidence[1]` as joint_conf when `evidence` is on - and keeps (smooth, track_poses,
-        # track_state) in `last_smooth`; the returned tuple is the same either way.  None: no launch more than without it.
-        self.smoother = None
-        self.last_smooth = None
-        # a utils.overlay.PoseOverlay (needs `evidence` and uint8 camera frames as `views`, or, built with nv12=True,
-        # Nv12Frames views, whose surface is then the canvas): forward() also draws the
-        # skeletons into the caller's frames, in place, behind the tracker and the smoother - from `last_evidence[0]`, or,
-        # with a smoother, from one more joint_evidence() of `last_smooth[0]` kept in `last_overlay_views` - with
-        # `last_tracks[0]` as colour keys and `last_evidence[1]` as joint_conf; the returned tuple is the same either way.
-        # None: no launch more than without it.
-        self.overlay = None
-        self.last_overlay_views = None
-        # a utils.crops.PersonCrops (needs `evidence` and uint8 camera frames or Nv12Frames as `views`): forward() also
-        # cuts a patch per (frame, view, person) out of the caller's frames behind the tracker and the smoother and BEFORE the
-        # overlay draws (clean pixels) - boxes from the pixels the overlay would draw (`last_evidence[0]`, or, with a smoother,
-        # the one extra joint_evidence() of `last_smooth[0]` in `last_overlay_views`, issued once for both), `last_tracks[0]` as
-        # ids and `last_evidence[1]` as joint_conf - and keeps (patches, rois, count, score) in `last_crops`; the returned
-        # tuple is the same either way.  None: no launch more than without it.
-        self.crops = None
-        self.last_crops = None
-        # a utils.visibility.JointVisibility (needs `evidence`): forward() also tests every fused joint's line of sight to
-        # every camera against the other people's bodies, right behind the evidence launch, on `last_evidence[0]` and the
-        # engine's camera tables, and keeps (occluder, vis_conf, vis_count) in `last_visibility`.  Built with feeds_conf=True
-        # (the default), `vis_conf` takes the place of `last_evidence[1]` as the joint_conf of smoother, overlay and crops;
-        # the returned tuple is the same either way.  None: no launch more than without it.
-        self.visibility = None
-        self.last_visibility = None
-        # a utils.triangulate.JointTriangulator: forward() also triangulates every fused joint from the heat-map peaks of the
-        # views, behind the evidence and visibility launches, on the staging copy of this forward and the engine's camera
-        # tables - with `last_visibility[0]` as the occluder table when `visibility` is set - and keeps (tri_poses, tri_count,
-        # tri_stats, obs, view_state, cam_resid, cam_count) in `last_triangulation`.  The poses handed to tracker, smoother,
-        # overlay and crops stay the fused ones (feeding tri_poses onward is not built); the returned tuple is the same either
-        # way.  None: no launch more than without it.
-        self.triangulator = None
-        self.last_triangulation = None
-        # a utils.recalibrate.CameraRefiner (needs `triangulator`): forward() also adds this batch's observations to the
-        # refiner's accumulators - one launch right behind the triangulation's, on `last_triangulation` and the engine's
-        # camera tables; `recalibrator_points`: "fused" (the forward's joints) or "tri" (the triangulated ones) as the 3-D
-        # points.  Solving and adopting stay with the caller (`recalibrator.solve(engine.geo.cams)`, `camera_dicts`): the
-        # engine's tables are never swapped here.  The returned tuple is the same either way.  None: no launch more.
-        self.recalibrator = None
+        for stage in STAGES:                             # every optional stage unset (STAGES says what each does when set)
+            setattr(self, stage.attr, None)
+            if stage.last is not None:
+                setattr(self, stage.last, None)
         self.recalibrator_points = "fused"
         self.eval()
 
@@ -124,151 +131,138 @@ class FasterVoxelPoseNet(nn.Module):
         synchronisation."""
         return self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform)
 
+    def _check_needs(self, stage, views):
+        """FvpError unless everything ``stage`` (a row of STAGES, set on this model) needs is there as well."""
+        for need, why in stage.needs.items():
+            if need == "evidence":
+                ok = self.evidence
+            elif need == "frames":
+                # an NV12 surface is the decoder's own memory: drawn on only by an overlay built with nv12=True
+                ok = getattr(getattr(self, stage.attr), "nv12", True) if isinstance(views, Nv12Frames) \
+                    else torch.is_tensor(views) and views.dtype == torch.uint8
+            else:
+                ok = getattr(self, need) is not None
+            if not ok:
+                raise capi.FvpError(f"model.{stage.attr} {why}: {_REMEDY[need]}")
+
+    def _heatmaps_from_views(self, backbone, views, resize_transform):
+        """``views`` - fp32 images [B,V,3,H,W], uint8 camera frames [B,V,Hs,Ws,3] or an ``Nv12Frames`` with leading
+        dimensions [B,V] (dataset/images.py) - through ``backbone`` -> ``input_heatmaps`` [B,V,J,H/4,W/4]."""
+        nv12 = isinstance(views, Nv12Frames)              # a decoder's NV12 surface
+        frames = not nv12 and views.dtype == torch.uint8  # raw camera frames
+        if nv12:
+            if len(views.lead) != 2:
+                raise capi.FvpError(f"NV12 views must have leading dimensions [B,V], got {views.lead}")
+            if resize_transform is None:
+                raise capi.FvpError("NV12 views need resize_transform (camera -> network pixels) to be resized")
+            B, V = views.lead
+        else:
+            if frames:
+                if views.dim() != 5 or views.shape[-1] != 3:
+                    raise capi.FvpError(f"uint8 views must be camera frames [B,V,Hs,Ws,3] (HWC), got {tuple(views.shape)}")
+                if resize_transform is None:
+                    raise capi.FvpError("uint8 views need resize_transform (camera -> network pixels) to be resized")
+            B, V = views.shape[:2]
+        if hasattr(backbone, "_run"):
+            # bf16 HIP backbone (models/resnet.py): all B*V views in one pass - frames and surfaces through the ingest kernel
+            # straight into its bf16 input, no RGB frame and no fp32 image in between; it writes the heatmaps as NCHW
+            # (returned, like the reference) and in the channels-last layout the projection reads
+            nchw, cl = backbone._run(views if nv12 else views.flatten(0, 1), True, True,
+                                     resize_transform=resize_transform if nv12 or frames else None)
+            input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
+            if cl.shape[-1] == self.engine.JP:
+                self.engine.adopt_staging(input_heatmaps, cl)
+            return input_heatmaps
+        # any torch module: the fp32 tensor the reference's loader would have produced, then per-view passes (:36-38)
+        if nv12:
+            views = ingest_nv12(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+        elif frames:
+            views = ingest_frames(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+        return torch.stack([backbone(views[:, c]) for c in range(V)], dim=1)
+
     def forward(self, backbone=None, views=None, meta=None, targets=None, input_heatmaps=None, cameras=None,
                 resize_transform=None):
         if self.training:
             raise NotImplementedError("only the inference branch of FasterVoxelPoseNet.forward is implemented "
                                       "(call model.eval()); training losses are outside the hot path")
-        if self.smoother is not None and self.tracker is None:
-            raise capi.FvpError("model.smoother filters the tracks of model.tracker: set model.tracker (a PoseTracker) too")
-        if self.visibility is not None and not self.evidence:
-            raise capi.FvpError("model.visibility judges the pixels of model.last_evidence: set model.evidence = True too")
-        canvas = None
-        if self.overlay is not None:
-            if not self.evidence:
-                raise capi.FvpError("model.overlay draws the pixels of model.last_evidence: set model.evidence = True too")
-            # an NV12 surface is the decoder's own memory: drawn on only by an overlay built with nv12=True
-            if not (isinstance(views, Nv12Frames) and self.overlay.nv12) \
-                    and (not torch.is_tensor(views) or views.dtype != torch.uint8):
-                raise capi.FvpError("model.overlay draws into the camera frames: pass them as views, uint8 [B,V,Hs,Ws,3] "
-                                    "(NV12 surfaces, float images and input_heatmaps alone leave nothing to draw on; "
-                                    "PoseOverlay(..., nv12=True) draws into Nv12Frames views, in the surface itself)")
-            canvas = views
-        source = None
-        if self.crops is not None:
-            if not self.evidence:
-                raise capi.FvpError("model.crops cuts around the pixels of model.last_evidence: set model.evidence = True too")
-            if not isinstance(views, Nv12Frames) and (not torch.is_tensor(views) or views.dtype != torch.uint8):
-                raise capi.FvpError("model.crops cuts the patches out of the camera frames: pass them as views, uint8 "
-                                    "[B,V,Hs,Ws,3] or Nv12Frames (float images and input_heatmaps alone leave nothing to "
-                                    "cut from)")
-            source = views
+        for attr in _CHECKED_FIRST:
+            if getattr(self, attr) is not None:
+                self._check_needs(_STAGE[attr], views)
         if views is not None:
-            nv12 = isinstance(views, Nv12Frames)          # a decoder's NV12 surface, leading dimensions [B,V]
-            frames = not nv12 and views.dtype == torch.uint8          # raw camera frames [B,V,Hs,Ws,3] (dataset/images.py)
-            if nv12:
-                if len(views.lead) != 2:
-                    raise capi.FvpError(f"NV12 views must have leading dimensions [B,V], got {views.lead}")
-                if resize_transform is None:
-                    raise capi.FvpError("NV12 views need resize_transform (camera -> network pixels) to be resized")
-                B, V = views.lead
-                if hasattr(backbone, "_run"):
-                    # the ingest kernel reads the surface and writes the backbone's bf16 input: no RGB frame, no fp32 image
-                    nchw, cl = backbone._run(views, True, True, resize_transform=resize_transform)
-                    input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
-                    if cl.shape[-1] == self.engine.JP:
-                        self.engine.adopt_staging(input_heatmaps, cl)
-                else:
-                    views = ingest_nv12(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
-                    input_heatmaps = torch.stack([backbone(views[:, c]) for c in range(V)], dim=1)
-            elif frames:
-                if views.dim() != 5 or views.shape[-1] != 3:
-                    raise capi.FvpError(f"uint8 views must be camera frames [B,V,Hs,Ws,3] (HWC), got {tuple(views.shape)}")
-                if resize_transform is None:
-                    raise capi.FvpError("uint8 views need resize_transform (camera -> network pixels) to be resized")
-            if nv12:
-                pass                                      # done above; tensor views below take the path they took
-            elif frames and hasattr(backbone, "_run"):
-                # the ingest kernel writes the backbone's bf16 input directly: no fp32 image tensor
-                B, V = views.shape[:2]
-                nchw, cl = backbone._run(views.flatten(0, 1), True, True, resize_transform=resize_transform)
-                input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
-                if cl.shape[-1] == self.engine.JP:
-                    self.engine.adopt_staging(input_heatmaps, cl)
-            elif frames:
-                # any torch module: the fp32 tensor the reference's loader would have produced, then per-view passes
-                views = ingest_frames(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
-                input_heatmaps = torch.stack([backbone(views[:, c]) for c in range(views.shape[1])], dim=1)
-            elif hasattr(backbone, "_run"):
-                # bf16 HIP backbone (models/resnet.py): all B*V views in one pass; it writes the heatmaps as
-                # NCHW (returned, like the reference) and in the channels-last layout the projection reads
-                B, V = views.shape[:2]
-                nchw, cl = backbone._run(views.flatten(0, 1), True, True)
-                input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
-                if cl.shape[-1] == self.engine.JP:
-                    self.engine.adopt_staging(input_heatmaps, cl)
-            else:
-                # per-view backbone passes, as the reference (:36-38); any torch module
-                num_views = views.shape[1]
-                input_heatmaps = torch.stack([backbone(views[:, c]) for c in range(num_views)], dim=1)
+            input_heatmaps = self._heatmaps_from_views(backbone, views, resize_transform)
         _, _, proposal_centers, _ = self.pose_net(input_heatmaps, meta, cameras, resize_transform)
         mask = self.engine.last["valid"]              # uint8 [B,N] = proposal_centers[:, :, 3] >= 0 (:45), written by fvp_proposals
         fused_poses, plane_poses = self.joint_net.forward5(meta, input_heatmaps, proposal_centers, mask, cameras,
                                                            resize_transform, _reuse_staging=True)
+        self._run_stages(views, fused_poses, input_heatmaps, meta, cameras, resize_transform)
+        # the channels-last staging copy is valid for this call only: a later tensor may reuse the
+        # same address / version / shape once the caching allocator recycles the block
+        self.engine.invalidate_staging()
+        return fused_poses, plane_poses, proposal_centers, input_heatmaps, None
+
+    def _run_stages(self, views, fused_poses, input_heatmaps, meta, cameras, resize_transform):
+        """Evidence and the optional stages (STAGES) behind the fused poses, each one only when set: evidence, visibility,
+        triangulator, recalibrator, tracker, smoother, the evidence of the smoothed poses, crops, overlay."""
+        eng, V = self.engine, input_heatmaps.shape[1]
+        rows = []
+
+        def frame_set():
+            # the frames' camera-set rows, the engine's own table (cached, no upload here): fetched by the first stage that
+            # needs them, once
+            if not rows:
+                rows.append(eng.frame_sets(meta, cameras, V))
+            return rows[0]
+
+        conf = None
         if self.evidence:
-            # static-shape and sync-free like the rest of the forward: under GraphedForward / GraphedPipeline the launch is
-            # part of the captured graph and `last_evidence` holds static tensors, overwritten by the next replay
-            self.last_evidence = self.engine.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform,
-                                                            reuse_staging=True)
-        conf = self.last_evidence[1] if self.evidence else None
+            self.last_evidence = eng.joint_evidence(fused_poses, input_heatmaps, meta, cameras, resize_transform,
+                                                    reuse_staging=True)
+            conf = self.last_evidence[1]
         if self.visibility is not None:
-            # static-shape and sync-free as well: the body model travels by value, the camera tables are the engine's
-            vis = self.visibility
+            vis = self.visibility                         # the body model travels by value, the camera tables are the engine's
             ws, hs = self.cfg.DATASET.ORI_IMAGE_SIZE
-            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
-            self.last_visibility = vis(fused_poses, self.engine.geo.cams, fs, views=self.last_evidence[0],
+            self.last_visibility = vis(fused_poses, eng.geo.cams, frame_set(), views=self.last_evidence[0],
                                        frame_size=vis.frame_size or (hs, ws))
             if vis.feeds_conf:
                 conf = self.last_visibility[1]
         if self.triangulator is not None:
-            # static-shape and sync-free: the parameters travel by value, the outputs are the triangulator's own tensors
-            g = self.engine.geom(resize_transform)
-            g.V = input_heatmaps.shape[1]
-            fs = self.engine.frame_sets(meta, cameras, g.V)
-            hcl = self.engine.heat_cl(input_heatmaps, g, reuse=True)
+            g = eng.geom(resize_transform)                # the parameters travel by value, the outputs are the triangulator's own
+            g.V = V
+            fs = frame_set()
+            hcl = eng.heat_cl(input_heatmaps, g, reuse=True)
             occ = self.last_visibility[0] if self.visibility is not None else None
-            self.last_triangulation = self.triangulator(fused_poses, self.engine.geo.cams, fs, hcl, occluder=occ, geom=g)
+            self.last_triangulation = self.triangulator(fused_poses, eng.geo.cams, fs, hcl, occluder=occ, geom=g)
         if self.recalibrator is not None:
-            if self.triangulator is None:
-                raise capi.FvpError("model.recalibrator reads the triangulation's obs and view_state: set model.triangulator "
-                                    "= JointTriangulator(cfg) as well")
+            self._check_needs(_STAGE["recalibrator"], views)
             if self.recalibrator_points not in ("fused", "tri"):
                 raise capi.FvpError(f"model.recalibrator_points must be 'fused' or 'tri', got {self.recalibrator_points!r}")
             tri = self.last_triangulation
             pts = fused_poses if self.recalibrator_points == "fused" else tri[0]
-            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
-            self.recalibrator.accumulate(pts, tri[3], tri[4], self.engine.geo.cams, fs)
+            self.recalibrator.accumulate(pts, tri[3], tri[4], eng.geo.cams, frame_set())
         if self.tracker is not None:
-            # the frames' sequence rows are the engine's own table (frame_sets: cached, no upload here); static-shape and
-            # sync-free, so a captured graph holds the launch and the state in device memory carries from replay to replay
-            if len(self.engine.geo.seq_ids) > self.tracker.nseq:
-                raise capi.FvpError(f"the engine has seen {len(self.engine.geo.seq_ids)} sequences, model.tracker was "
+            if len(eng.geo.seq_ids) > self.tracker.nseq:
+                raise capi.FvpError(f"the engine has seen {len(eng.geo.seq_ids)} sequences, model.tracker was "
                                     f"built for nseq = {self.tracker.nseq}")
-            fs = self.engine.frame_sets(meta, cameras, input_heatmaps.shape[1])
-            self.last_tracks = self.tracker.update(fused_poses, sequences=fs)
+            self.last_tracks = self.tracker.update(fused_poses, sequences=frame_set())
             if self.smoother is not None:
                 if self.smoother.nseq < self.tracker.nseq:
                     raise capi.FvpError(f"model.smoother was built for nseq = {self.smoother.nseq}, model.tracker for "
                                         f"{self.tracker.nseq}")
                 self.last_smooth = self.smoother.update(fused_poses, self.last_tracks[0], self.last_tracks[1],
-                                                        joint_conf=conf, sequences=fs)
-        if canvas is not None or source is not None:
+                                                        joint_conf=conf, sequences=frame_set())
+        if self.crops is not None or self.overlay is not None:
             # ingest has read the frames on this stream already.  With a smoother the picture shows the steady poses:
             # their pixels are one more evidence launch on the staging copy of this forward, shared by crops and overlay
             px, self.last_overlay_views = self.last_evidence[0], None
             if self.smoother is not None:
-                px = self.engine.joint_evidence(self.last_smooth[0], input_heatmaps, meta, cameras, resize_transform,
-                                                reuse_staging=True)[0]
+                px = eng.joint_evidence(self.last_smooth[0], input_heatmaps, meta, cameras, resize_transform,
+                                        reuse_staging=True)[0]
                 self.last_overlay_views = px
             ids = self.last_tracks[0] if self.tracker is not None else None
-            if source is not None:                        # before the overlay paints: the patches hold clean pixels
-                self.last_crops = self.crops(source, px, ids=ids, joint_conf=conf)
-            if canvas is not None:
-                self.overlay.draw(canvas, px, ids=ids, joint_conf=conf)
-        # the channels-last staging copy is valid for this call only: a later tensor may reuse the
-        # same address / version / shape once the caching allocator recycles the block
-        self.engine.invalidate_staging()
-        return fused_poses, plane_poses, proposal_centers, input_heatmaps, None
+            if self.crops is not None:                    # before the overlay paints: the patches hold clean pixels
+                self.last_crops = self.crops(views, px, ids=ids, joint_conf=conf)
+            if self.overlay is not None:
+                self.overlay.draw(views, px, ids=ids, joint_conf=conf)
 
 
 class GraphedForward:
@@ -323,17 +317,10 @@ class PipelinedForward:
     ``event.wait()`` (or after ``synchronize()``).  Results are identical to the plain forward:
     every kernel is deterministic and replicas share nothing but read-only inputs.
 
-    Batches run on several streams and replicas, and a tracker needs the frames in time order on one stream: the
-    pipeline takes no ``model.tracker`` (the constructor refuses a model that has one).  Keep the ``PoseTracker`` beside
-    the pipeline and call ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after
-    ``event.wait()``.  A ``model.smoother`` is refused for the same reason; the consumer-stream recipe is
-    ``ids, slots, _ = tracker.update(outputs[0], meta)`` followed by ``smoother.update(outputs[0], ids, slots, meta=meta)``
-    (with ``joint_conf=model.joint_evidence(outputs[0], ...)[1]`` when joints are to be gated).  A ``model.overlay`` is
-    refused as well: ``overlay.draw(frames, views, ids)`` on the consumer stream, with ``views`` from
-    ``model.joint_evidence``.  So is a ``model.crops``: ``crops(frames, views, ids)`` on the consumer stream, before any
-    ``overlay.draw``.  And a ``model.visibility``: ``visibility(outputs[0], cameras, meta, views=views)`` there.  And a
-    ``model.triangulator``: ``triangulator(outputs[0], cameras, meta, heat_cl)`` there, and a ``model.recalibrator``:
-    ``recalibrator.accumulate(outputs[0], obs, view_state, cams, frame_set)`` behind it."""
+    Batches run on several streams and replicas, and the optional stages of ``STAGES`` need the frames in time order on
+    one stream (tracker, smoother, recalibrator) or read what only one replica holds: the constructor refuses a model with
+    any of them set.  Keep the stage objects beside the pipeline and call them on the consumer stream, in submit order,
+    after ``event.wait()`` - each row's ``recipe`` says how, and the refusal prints it."""
 
     def __init__(self, model, depth=2, streams=None, backpressure=True):
         """``streams``: optional list of >= depth ``torch.cuda.Stream`` to run on (a process that builds several pipelines
@@ -346,32 +333,10 @@ class PipelinedForward:
         the host time spent in that wait."""
         assert depth >= 1
         assert streams is None or len(streams) >= depth
-        if model.tracker is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.tracker = None "
-                                "and call tracker.update(outputs[0], meta) on the consumer stream in submit order")
-        if model.smoother is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.smoother = None "
-                                "and call smoother.update(outputs[0], ids, slots, meta=meta) behind tracker.update on the "
-                                "consumer stream in submit order")
-        if model.overlay is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.overlay = None "
-                                "and call overlay.draw(frames, views, ids) on the consumer stream")
-        if model.crops is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.crops = None "
-                                "and call crops(frames, views, ids) on the consumer stream, with views from "
-                                "model.joint_evidence(outputs[0], ...)[0], before any overlay.draw")
-        if model.visibility is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.visibility = None "
-                                "and call visibility(outputs[0], cameras, meta, views=views) on the consumer stream, with "
-                                "views from model.joint_evidence(outputs[0], ...)[0]")
-        if model.recalibrator is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.recalibrator = None "
-                                "and call recalibrator.accumulate(outputs[0], obs, view_state, cams, frame_set) behind the "
-                                "triangulator on the consumer stream")
-        if model.triangulator is not None:
-            raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set model.triangulator = None "
-                                "and call triangulator(outputs[0], cameras, meta, heat_cl) on the consumer stream, with "
-                                "heat_cl from model.engine.heat_cl(outputs[3], geom)")
+        for stage in STAGES:
+            if getattr(model, stage.attr) is not None:
+                raise capi.FvpError("PipelinedForward runs batches on several streams and replicas: set "
+                                    f"model.{stage.attr} = None and {stage.recipe}")
         self.models = [model]
         self.streams = list(streams[:depth]) if streams is not None else [torch.cuda.Stream(device=model.device) for _ in range(depth)]
         for _ in range(1, depth):
@@ -432,11 +397,9 @@ class GraphedPipeline:
     the outputs are the slot's static tensors, overwritten when the slot comes round again (``depth`` submits later): read
     or clone them before that.  Same kernels, same order per slot: results equal ``PipelinedForward`` bit for bit.
     Shapes, cameras and the sequence list are fixed at capture time (the reference's caller loop, function.py:136-148,
-    feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, a tracker
-    stays outside: ``tracker.update(outputs[0], meta)`` on the consumer stream, in submit order, after ``event.wait()``
-    (before the slot comes round again), and ``smoother.update(outputs[0], ids, slots, meta=meta)`` behind it; an overlay
-    likewise (``overlay.draw(frames, views, ids)`` on the consumer stream), and person crops (``crops(frames, views, ids)``
-    there, before the overlay draws)."""
+    feeds one sequence mix per run); a different shape needs a new pipeline.  As for ``PipelinedForward``, the optional
+    stages (``STAGES``) stay outside, on the consumer stream, in submit order, after ``event.wait()`` and before the slot
+    comes round again."""
 
     def __init__(self, model, depth, meta, input_heatmaps, cameras, resize_transform, streams=None, warmup=2):
         self.pipe = PipelinedForward(model, depth=depth, streams=streams)

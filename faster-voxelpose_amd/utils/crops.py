@@ -10,24 +10,16 @@ memory and streams only.
 Not built: rotated boxes, anti-aliased down-scaling (a crop that shrinks by more than 2 x aliases as the ingest does),
 I420 / P010 surfaces, compaction of the valid crops into a dense list, any appearance model.
 """
-import ctypes as C
 import math
 
 import torch
 
 from .. import _capi as capi
+from .._args import f3, load_lib, require_gpu, stream_ptr, tensor_arg
+from .._args import ptr as _ptr
 from ..dataset.images import IMAGENET_MEAN, IMAGENET_STD, Nv12Frames
 
 MAX_PEOPLE = 32                                          # the limit of fvp_person_rois
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f3(v):
-    v = [float(x) for x in v]
-    return (C.c_float * 3)(*v)
 
 
 class PersonCrops:
@@ -48,9 +40,7 @@ class PersonCrops:
 
     def __init__(self, num_joints_or_cfg, size=(256, 192), scale=1.25, pad_px=0.0, min_joints=2, joints=None, conf_min=0.0,
                  mean=IMAGENET_MEAN, std=IMAGENET_STD, bf16=False, swap_rb=False, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         J = num_joints_or_cfg if isinstance(num_joints_or_cfg, int) else num_joints_or_cfg.DATASET.NUM_JOINTS
         self.J = int(J)
         if not 1 <= self.J <= capi.FVP_MAX_JOINTS:
@@ -80,10 +70,7 @@ class PersonCrops:
                 or any(v == 0 for v in self.std):
             raise capi.FvpError(f"mean and std: three finite values each, std non-zero (mean = {mean}, std = {std})")
         self.bf16, self.swap_rb = bool(bf16), bool(swap_rb)
-        self._mean, self._std = _f3(self.mean), _f3(self.std)
-
-    def _stream(self, device):
-        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
+        self._mean, self._std = f3(self.mean), f3(self.std)
 
     def rois(self, views, ids=None, joint_conf=None):
         """``views [B,V,N,J,4]`` (``last_evidence[0]``, or ``joint_evidence(...)[0]`` of any poses) -> ``(rois [B,V,N,4]``
@@ -91,31 +78,19 @@ class PersonCrops:
         ``score [B,V,N]`` fp32, their mean heatmap support in that view``)``.  ``ids [B,N]`` int32 (``last_tracks[0]``):
         slots with a negative id get no box; ``joint_conf [B,N,J]`` (``last_evidence[1]``): joints below ``conf_min`` are
         not usable.  A box without ``min_joints`` usable joints is zeros in all three.  One launch on the current stream."""
-        v = views
-        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 5 or tuple(v.shape[3:]) != (self.J, 4) \
-                or not v.is_contiguous():
-            raise capi.FvpError(f"views must be a contiguous float32 tensor [B,V,N,{self.J},4] (what joint_evidence returns), "
-                                f"got {getattr(v, 'dtype', type(v))} {tuple(getattr(v, 'shape', ()))}")
-        if not self._injected and v.device.type != "cuda":
-            raise capi.FvpError(f"views live on {v.device}: the boxes are computed on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
+        v = tensor_arg("views", views, torch.float32, ("B", "V", "N", self.J, 4), hint="what joint_evidence returns")
+        require_gpu("the box computation", v.device, self._injected)
         B, V, N = v.shape[:3]
         if not 1 <= N <= MAX_PEOPLE or V > capi.FVP_MAX_VIEWS:
             raise capi.FvpError(f"PersonCrops.rois limits: 1 <= N <= {MAX_PEOPLE}, V <= {capi.FVP_MAX_VIEWS} (N = {N}, V = {V})")
-        if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != v.device
-                                or tuple(ids.shape) != (B, N) or not ids.is_contiguous()):
-            raise capi.FvpError(f"ids must be a contiguous int32 tensor [{B},{N}] on {v.device} (what PoseTracker.update "
-                                "returns)")
-        c = joint_conf
-        if c is not None and (not torch.is_tensor(c) or c.dtype != torch.float32 or c.device != v.device
-                              or tuple(c.shape) != (B, N, self.J) or not c.is_contiguous()):
-            raise capi.FvpError(f"joint_conf must be a contiguous float32 tensor [{B},{N},{self.J}] on {v.device}")
+        tensor_arg("ids", ids, torch.int32, (B, N), v.device, hint="what PoseTracker.update returns", optional=True)
+        c = tensor_arg("joint_conf", joint_conf, torch.float32, (B, N, self.J), v.device, optional=True)
         rois = torch.empty((B, V, N, 4), dtype=torch.float32, device=v.device)
         count = torch.empty((B, V, N), dtype=torch.int32, device=v.device)
         score = torch.empty((B, V, N), dtype=torch.float32, device=v.device)
         rc = self.lib.fvp_person_rois(_ptr(v), _ptr(ids), _ptr(c), B, V, N, self.J, self.joint_mask, self.min_joints,
                                       self.scale, self.pad_px, self.aspect, self.conf_min, _ptr(rois), _ptr(count),
-                                      _ptr(score), self._stream(v.device))
+                                      _ptr(score), stream_ptr(v.device))
         capi.check(self.lib, rc, "fvp_person_rois")
         return rois, count, score
 
@@ -131,18 +106,13 @@ class PersonCrops:
             if len(f.lead) != 2:
                 raise capi.FvpError(f"an NV12 surface to crop from must have leading dimensions [B,V], got {f.lead}")
             B, V, Hs, Ws = f.lead[0], f.lead[1], f.Hs, f.Ws
-        elif not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3 or not f.is_contiguous():
-            raise capi.FvpError("frames must be a contiguous uint8 tensor [B,V,Hs,Ws,3] (HWC camera frames) or Nv12Frames, "
-                                f"got {getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))}")
-        if not self._injected and f.device.type != "cuda":
-            raise capi.FvpError(f"frames live on {f.device}: the crop runs on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
-        if not nv12:
-            B, V, Hs, Ws = f.shape[:4]
-        if not torch.is_tensor(r) or r.dtype != torch.float32 or r.device != f.device or r.dim() != 4 \
-                or tuple(r.shape[:2]) != (B, V) or r.shape[3] != 4 or r.shape[2] < 1 or not r.is_contiguous():
-            raise capi.FvpError(f"rois must be a contiguous float32 tensor [{B},{V},K,4] on {f.device} with K >= 1 (what "
-                                f"rois() returns), got {getattr(r, 'dtype', type(r))} {tuple(getattr(r, 'shape', ()))}")
+        else:
+            B, V, Hs, Ws = tensor_arg("frames", f, torch.uint8, ("B", "V", "Hs", "Ws", 3),
+                                      hint="HWC camera frames; or Nv12Frames").shape[:4]
+        require_gpu("the crop", f.device, self._injected)
+        r = tensor_arg("rois", r, torch.float32, (B, V, "K", 4), f.device, hint="what rois() returns")
+        if r.shape[2] < 1:
+            raise capi.FvpError(f"rois must hold K >= 1 boxes per frame and view, got {tuple(r.shape)}")
         if nv12 and self.swap_rb:
             raise capi.FvpError("swap_rb is for RGB frames: an NV12 surface converts to R, G, B in that order")
         K = r.shape[2]
@@ -156,11 +126,11 @@ class PersonCrops:
         if nv12:
             rc = self.lib.fvp_crop_rois_nv12(_ptr(f.y), _ptr(f.uv), B * V, Hs, Ws, f.y_pitch, f.uv_pitch, f.y_frame_stride,
                                              f.uv_frame_stride, f.standard, _ptr(r), R, K, self._mean, self._std, self.h,
-                                             self.w, o16, o32, self._stream(f.device))
+                                             self.w, o16, o32, stream_ptr(f.device))
             capi.check(self.lib, rc, "fvp_crop_rois_nv12")
             return out
         rc = self.lib.fvp_crop_rois(_ptr(f), B * V, Hs, Ws, _ptr(r), R, K, self._mean, self._std, self.h, self.w,
-                                    capi.INGEST_SWAP_RB if self.swap_rb else 0, o16, o32, self._stream(f.device))
+                                    capi.INGEST_SWAP_RB if self.swap_rb else 0, o16, o32, stream_ptr(f.device))
         capi.check(self.lib, rc, "fvp_crop_rois")
         return out
 

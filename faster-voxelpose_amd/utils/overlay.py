@@ -13,6 +13,8 @@ import ctypes as C
 import torch
 
 from .. import _capi as capi
+from .._args import load_lib, require_gpu, stream_ptr, tensor_arg
+from .._args import ptr as _ptr
 from ..dataset.images import Nv12Frames
 
 # person colours, RGB, indexed by track id (or by slot without ids) modulo the length
@@ -20,10 +22,6 @@ PALETTE = [(230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 13
            (240, 50, 230), (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255), (170, 110, 40), (255, 250, 200),
            (128, 0, 0), (170, 255, 195)]
 MAX_PEOPLE, MAX_LIMBS, MAX_COLOURS, MAX_Q4 = 32, 64, 64, 1024          # the limits of fvp_draw_poses
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class PoseOverlay:
@@ -45,9 +43,7 @@ class PoseOverlay:
 
     def __init__(self, num_joints_or_cfg, limbs=None, palette=None, joint_radius=8.0, limb_width=4.0, alpha=1.0,
                  conf_min=0.0, nv12=False, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         J = num_joints_or_cfg if isinstance(num_joints_or_cfg, int) else num_joints_or_cfg.DATASET.NUM_JOINTS
         self.J = int(J)
         if not 1 <= self.J <= capi.FVP_MAX_JOINTS:
@@ -93,31 +89,17 @@ class PoseOverlay:
             if len(f.lead) != 2:
                 raise capi.FvpError(f"an NV12 surface to draw on must have leading dimensions [B,V], got {f.lead}")
             B, V, Hs, Ws = f.lead[0], f.lead[1], f.Hs, f.Ws
-        elif not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3 or not f.is_contiguous():
-            raise capi.FvpError("frames must be a contiguous uint8 tensor [B,V,Hs,Ws,3] (HWC camera frames), got "
-                                f"{getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))}")
-        if not self._injected and f.device.type != "cuda":
-            raise capi.FvpError(f"frames live on {f.device}: the overlay runs on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
-        if not nv12:
-            B, V, Hs, Ws = f.shape[:4]
-        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.device != f.device or v.dim() != 5 \
-                or tuple(v.shape[:2]) != (B, V) or tuple(v.shape[3:]) != (self.J, 4) or not v.is_contiguous():
-            raise capi.FvpError(f"views must be a contiguous float32 tensor [{B},{V},N,{self.J},4] on {f.device} (what "
-                                f"joint_evidence returns), got {getattr(v, 'dtype', type(v))} {tuple(getattr(v, 'shape', ()))}")
+        else:
+            B, V, Hs, Ws = tensor_arg("frames", f, torch.uint8, ("B", "V", "Hs", "Ws", 3), hint="HWC camera frames").shape[:4]
+        require_gpu("the overlay", f.device, self._injected)
+        v = tensor_arg("views", v, torch.float32, (B, V, "N", self.J, 4), f.device, hint="what joint_evidence returns")
         N = v.shape[2]
         if not 1 <= N <= MAX_PEOPLE or V > capi.FVP_MAX_VIEWS or min(Hs, Ws) < 1:
             raise capi.FvpError(f"PoseOverlay.draw limits: 1 <= N <= {MAX_PEOPLE}, V <= {capi.FVP_MAX_VIEWS}, Hs, Ws >= 1 "
                                 f"(N = {N}, V = {V}, Hs = {Hs}, Ws = {Ws})")
-        if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != f.device
-                                or tuple(ids.shape) != (B, N) or not ids.is_contiguous()):
-            raise capi.FvpError(f"ids must be a contiguous int32 tensor [{B},{N}] on {f.device} (what PoseTracker.update "
-                                "returns)")
-        c = joint_conf
-        if c is not None and (not torch.is_tensor(c) or c.dtype != torch.float32 or c.device != f.device
-                              or tuple(c.shape) != (B, N, self.J) or not c.is_contiguous()):
-            raise capi.FvpError(f"joint_conf must be a contiguous float32 tensor [{B},{N},{self.J}] on {f.device}")
-        stream = C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream) if f.device.type == "cuda" else None
+        tensor_arg("ids", ids, torch.int32, (B, N), f.device, hint="what PoseTracker.update returns", optional=True)
+        c = tensor_arg("joint_conf", joint_conf, torch.float32, (B, N, self.J), f.device, optional=True)
+        stream = stream_ptr(f.device)
         if nv12:
             rc = self.lib.fvp_draw_poses_nv12(_ptr(f.y), _ptr(f.uv), B, V, Hs, Ws, f.y_pitch, f.uv_pitch, f.y_frame_stride,
                                               f.uv_frame_stride, f.standard, _ptr(v), _ptr(ids), _ptr(c), N, self.J,

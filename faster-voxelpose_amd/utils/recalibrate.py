@@ -11,19 +11,16 @@ Not built: intrinsics or lens re-fit, joint refinement of points and cameras (bu
 camera is re-fitted at once, swapping the corrected tables into a running engine (its fine-grid cache depends on them: pass
 ``camera_dicts(...)`` into the forward under a new sequence name instead).
 """
-import ctypes as C
 import math
 
 import torch
 
 from .. import _capi as capi
+from .._args import load_lib, require_gpu, stream_ptr, tensor_arg
+from .._args import ptr as _ptr
 
 ACC = capi.FVP_CAL_ACC
 OK, CLAMPED, FEW, DEGENERATE = capi.FVP_CAL_OK, capi.FVP_CAL_CLAMPED, capi.FVP_CAL_FEW, capi.FVP_CAL_DEGENERATE
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class CameraRefiner:
@@ -43,9 +40,7 @@ class CameraRefiner:
 
     def __init__(self, cfg, nseq=1, undistort_iters=8, huber_px=0.0, decay=1.0, min_obs=60, lam=0.0, min_pivot=1e-9,
                  max_angle_deg=5.0, max_shift_mm=200.0, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         self.J = int(cfg.DATASET.NUM_JOINTS)
         if not 1 <= self.J <= capi.FVP_MAX_JOINTS:
             raise capi.FvpError(f"CameraRefiner needs 1 <= J <= {capi.FVP_MAX_JOINTS}, got {self.J}")
@@ -98,30 +93,17 @@ class CameraRefiner:
         return self._out[key]
 
     def _check_cams(self, cams, device=None):
-        if not torch.is_tensor(cams) or cams.dtype != torch.float32 or cams.dim() != 3 or cams.shape[0] < 1 \
-                or cams.shape[2] != capi.FVP_CAM_FLOATS or not cams.is_contiguous() or (device is not None and cams.device != device):
-            raise capi.FvpError(f"cams must be a contiguous float32 tensor [nsets,V,{capi.FVP_CAM_FLOATS}]"
-                                f"{'' if device is None else f' on {device}'}, got {getattr(cams, 'dtype', type(cams))} "
-                                f"{tuple(getattr(cams, 'shape', ()))}")
-        if not self._injected and cams.device.type != "cuda":
-            raise capi.FvpError(f"cams live on {cams.device}: the re-fit runs on a ROCm GPU device (spelled 'cuda:N' in "
-                                "PyTorch-ROCm); there is no CPU fallback")
-        if not 1 <= cams.shape[1] <= capi.FVP_MAX_VIEWS:
-            raise capi.FvpError(f"CameraRefiner limits: 1 <= V <= {capi.FVP_MAX_VIEWS} (V = {cams.shape[1]})")
-
-    def _stream(self, device):
-        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
+        tensor_arg("cams", cams, torch.float32, ("nsets", "V", capi.FVP_CAM_FLOATS), device)
+        require_gpu("the re-fit", cams.device, self._injected)
+        if cams.shape[0] < 1 or not 1 <= cams.shape[1] <= capi.FVP_MAX_VIEWS:
+            raise capi.FvpError(f"CameraRefiner limits: nsets >= 1, 1 <= V <= {capi.FVP_MAX_VIEWS} (cams {tuple(cams.shape)})")
 
     # ---- the two calls ----------------------------------------------------------------------------------------------
     def accumulate(self, points, obs, view_state, cams, frame_set):
         """One launch: the observations of one batch into the accumulators.  ``points [B,N,J,5]`` (``fused_poses`` or
         ``tri_poses``), ``obs [B,V,N,J,4]`` and ``view_state [B,V,N,J]`` int32 as ``JointTriangulator`` left them for the
         same batch, ``cams [nsets,V,24]`` and ``frame_set [B]`` int32 (the engine's tables)."""
-        p = points
-        if not torch.is_tensor(p) or p.dtype != torch.float32 or p.dim() != 4 or tuple(p.shape[2:]) != (self.J, 5) \
-                or not p.is_contiguous():
-            raise capi.FvpError(f"points must be a contiguous float32 tensor [B,N,{self.J},5], got "
-                                f"{getattr(p, 'dtype', type(p))} {tuple(getattr(p, 'shape', ()))}")
+        p = tensor_arg("points", points, torch.float32, ("B", "N", self.J, 5))
         self._check_cams(cams, p.device)
         B, N = p.shape[:2]
         nsets, V = cams.shape[:2]
@@ -130,15 +112,13 @@ class CameraRefiner:
         for name, t, dt, shape in (("obs", obs, torch.float32, (B, V, N, self.J, 4)),
                                    ("view_state", view_state, torch.int32, (B, V, N, self.J)),
                                    ("frame_set", frame_set, torch.int32, (B,))):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != p.device or tuple(t.shape) != shape or not t.is_contiguous():
-                raise capi.FvpError(f"{name} must be a contiguous {dt} tensor {list(shape)} on {p.device}, got "
-                                    f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+            tensor_arg(name, t, dt, shape, p.device)
         acc = self._state(nsets, V, p.device)
         if B == 0:
             return acc                                  # (an empty tensor has no address to pass)
         rc = self.lib.fvp_camera_refit_accumulate(_ptr(p), _ptr(obs), _ptr(view_state), _ptr(cams), nsets, _ptr(frame_set), B,
                                                   V, N, self.J, self.undistort_iters, self.huber_px, self.decay, _ptr(acc),
-                                                  self._stream(p.device))
+                                                  stream_ptr(p.device))
         capi.check(self.lib, rc, "fvp_camera_refit_accumulate")
         return acc
 
@@ -160,7 +140,7 @@ class CameraRefiner:
         out = slot[0][use]
         rc = self.lib.fvp_camera_refit_solve(_ptr(acc), _ptr(cams), nsets, V, self.min_obs, self.lam, self.min_pivot,
                                              self.max_angle_rad, self.max_shift_mm, *[_ptr(t) for t in out],
-                                             self._stream(cams.device))
+                                             stream_ptr(cams.device))
         capi.check(self.lib, rc, "fvp_camera_refit_solve")
         return out
 

@@ -16,14 +16,11 @@ import numpy as np
 import torch
 
 from .. import _capi as capi
-from .visibility import JointVisibility
+from .._args import CameraTables, load_lib, require_gpu, resolve_cameras, stream_ptr, tensor_arg
+from .._args import ptr as _ptr
 
 MAX_RADIUS = capi.FVP_TRI_MAX_RADIUS
 OUTPUTS = ("tri_poses", "tri_count", "tri_stats", "obs", "view_state", "cam_resid", "cam_count")
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class JointTriangulator:
@@ -41,13 +38,9 @@ class JointTriangulator:
     ``resize_transform`` the 2x3 camera -> network pixel transform; default: the dataset constant of ``cfg``.
     The defaults are guesses: no dataset was on hand to tune them."""
 
-    _tables = JointVisibility._tables      # the same upload-once camera tables (reads _seq_ids, _cams, _frame_sets)
-
     def __init__(self, cfg, radius=3, min_peak=0.3, undistort_iters=8, min_views=2, min_det=1e-3, reject_px=0.0,
                  per_camera=True, resize_transform=None, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         ds = cfg.DATASET
         self.J = int(ds.NUM_JOINTS)
         if not 1 <= self.J <= capi.FVP_MAX_JOINTS:
@@ -65,17 +58,8 @@ class JointTriangulator:
             resize_transform = get_resize_transform(ds.ORI_IMAGE_SIZE, ds.IMAGE_SIZE)
         if torch.is_tensor(resize_transform):
             resize_transform = resize_transform.detach().cpu()
-        rt = np.asarray(resize_transform, np.float32).reshape(6)
-        g = capi.FvpGeom()
-        g.clamp_max = float(max(ds.ORI_IMAGE_SIZE[0], ds.ORI_IMAGE_SIZE[1]))
-        for i in range(6):
-            g.rt[i] = float(rt[i])
-        g.W, g.H = int(ds.HEATMAP_SIZE[0]), int(ds.HEATMAP_SIZE[1])
-        g.hm_w, g.hm_h = float(g.W), float(g.H)
-        g.img_w, g.img_h = float(ds.IMAGE_SIZE[0]), float(ds.IMAGE_SIZE[1])
-        g.V, g.J, g.JP = 0, self.J, 4 * ((self.J + 3) // 4)
-        self.geom = g
-        self._seq_ids, self._cams, self._frame_sets = {}, None, {}
+        self.geom = capi.make_geom(ds, np.asarray(resize_transform, np.float32).reshape(6), self.J)
+        self._cameras = CameraTables()                 # of the sequences handed in as camera dicts
         self._out = {}
 
     def outputs(self, B, V, N, device):
@@ -107,47 +91,22 @@ class JointTriangulator:
         ``occluder [B,V,N,J]`` int32 (``last_visibility[0]``): only views with -1 are used.  ``ids [B,N]`` int32
         (``last_tracks[0]``): a slot with a negative id is not evaluated.  ``geom``: an ``FvpGeom`` to use instead of the one
         built from ``cfg`` (the engine's, with the forward's resize transform)."""
-        p, h = fused_poses, heat_cl
-        if not torch.is_tensor(p) or p.dtype != torch.float32 or p.dim() != 4 or tuple(p.shape[2:]) != (self.J, 5) \
-                or not p.is_contiguous():
-            raise capi.FvpError(f"fused_poses must be a contiguous float32 tensor [B,N,{self.J},5], got "
-                                f"{getattr(p, 'dtype', type(p))} {tuple(getattr(p, 'shape', ()))}")
-        if not self._injected and p.device.type != "cuda":
-            raise capi.FvpError(f"fused_poses live on {p.device}: the triangulation runs on a ROCm GPU device (spelled "
-                                "'cuda:N' in PyTorch-ROCm); there is no CPU fallback")
+        p = tensor_arg("fused_poses", fused_poses, torch.float32, ("B", "N", self.J, 5))
+        require_gpu("the triangulation", p.device, self._injected)
         B, N = p.shape[:2]
         g = self.geom if geom is None else geom
-        if not torch.is_tensor(h) or h.dtype != torch.float32 or h.device != p.device or h.dim() != 5 or h.shape[0] != B \
-                or tuple(h.shape[2:]) != (g.H, g.W, g.JP) or not h.is_contiguous():
-            raise capi.FvpError(f"heat_cl must be a contiguous float32 tensor [{B},V,{g.H},{g.W},{g.JP}] on {p.device} (the "
-                                f"channels-last staging copy), got {getattr(h, 'dtype', type(h))} {tuple(getattr(h, 'shape', ()))}")
-        V = h.shape[1]
-        if torch.is_tensor(cameras_or_cams):
-            cams, fs = cameras_or_cams, frame_set_or_meta
-            if cams.dtype != torch.float32 or cams.device != p.device or cams.dim() != 3 or cams.shape[0] < 1 \
-                    or tuple(cams.shape[1:]) != (V, capi.FVP_CAM_FLOATS) or not cams.is_contiguous():
-                raise capi.FvpError(f"cams must be a contiguous float32 tensor [nsets,{V},{capi.FVP_CAM_FLOATS}] on {p.device}, "
-                                    f"got {cams.dtype} {tuple(cams.shape)}")
-            if not torch.is_tensor(fs) or fs.dtype != torch.int32 or fs.device != p.device or tuple(fs.shape) != (B,) \
-                    or not fs.is_contiguous():
-                raise capi.FvpError(f"with a cams tensor, the frames' camera sets must be a contiguous int32 tensor [{B}] on "
-                                    f"{p.device}")
-        else:
-            seqs = frame_set_or_meta["seq"] if isinstance(frame_set_or_meta, dict) else frame_set_or_meta
-            if len(seqs) != B:
-                raise capi.FvpError(f"{len(seqs)} sequence names for {B} frames")
-            cams, fs = self._tables(cameras_or_cams, seqs, V, p.device)
+        h = tensor_arg("heat_cl", heat_cl, torch.float32, (B, "V", g.H, g.W, g.JP), p.device,
+                       hint="the channels-last staging copy")
+        cams, fs, V = resolve_cameras(self._cameras, cameras_or_cams, frame_set_or_meta, B, h.shape[1], p.device)
         if not 1 <= V <= capi.FVP_MAX_VIEWS or N < 1:
             raise capi.FvpError(f"JointTriangulator limits: N >= 1, 1 <= V <= {capi.FVP_MAX_VIEWS} (N = {N}, V = {V})")
-        for name, t, shape in (("occluder", occluder, (B, V, N, self.J)), ("ids", ids, (B, N))):
-            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.int32 or t.device != p.device
-                                  or tuple(t.shape) != shape or not t.is_contiguous()):
-                raise capi.FvpError(f"{name} must be a contiguous int32 tensor {list(shape)} on {p.device}")
+        tensor_arg("occluder", occluder, torch.int32, (B, V, N, self.J), p.device, optional=True)
+        tensor_arg("ids", ids, torch.int32, (B, N), p.device, optional=True)
         out = self.outputs(B, V, N, p.device)
         if B == 0:
             return out                                  # all empty (an empty tensor has no address to pass)
         g.V = V
-        stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream) if p.device.type == "cuda" else None
+        stream = stream_ptr(p.device)
         rc = self.lib.fvp_triangulate_joints(_ptr(h), _ptr(cams), cams.shape[0], _ptr(fs), _ptr(p), _ptr(ids), _ptr(occluder),
                                              B, N, C.byref(g), self.radius, self.min_peak, self.undistort_iters,
                                              self.min_views, self.min_det, self.reject_px, *[_ptr(t) for t in out], stream)

@@ -12,16 +12,13 @@ Not built: occlusion by scene objects, soft visibility, a per-view mask inside `
 import ctypes as C
 import math
 
-import numpy as np
 import torch
 
 from .. import _capi as capi
+from .._args import CameraTables, load_lib, require_gpu, resolve_cameras, stream_ptr, tensor_arg
+from .._args import ptr as _ptr
 
 MAX_PEOPLE, MAX_PRIMS = capi.FVP_VIS_MAX_PEOPLE, capi.FVP_VIS_MAX_PRIMS      # the limits of fvp_joint_visibility
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class JointVisibility:
@@ -40,9 +37,7 @@ class JointVisibility:
     dataset was on hand to tune them, and nothing here measures how often the verdict matches a labelled occlusion."""
 
     def __init__(self, num_joints_or_cfg, prims=None, radius=50.0, spheres=None, guard=60.0, feeds_conf=True, _lib=None):
-        # `_lib` is a test seam (tests/hipemu); the product always loads libfvp_hip.so
-        self._injected = _lib is not None
-        self.lib = _lib if _lib is not None else capi.load()
+        self.lib, self._injected = load_lib(_lib)
         self.frame_size = None
         if isinstance(num_joints_or_cfg, int):
             J = num_joints_or_cfg
@@ -80,26 +75,8 @@ class JointVisibility:
         L = len(pairs)
         self._prims = (C.c_int32 * max(2 * L, 1))(*[j for ab in pairs for j in ab])
         self._radius = (C.c_float * max(L, 1))(*radii)
-        self._seq_ids, self._cams, self._frame_sets = {}, None, {}
-
-    def _tables(self, cameras, seqs, V, device):
-        """Camera dicts and sequence names -> (cams [nsets,V,24], frame_set [B]), uploaded once per new sequence / list."""
-        from ..engine import HotPath
-        seqs = tuple(seqs)
-        for s in dict.fromkeys(seqs):
-            if s not in self._seq_ids:
-                if s not in cameras or len(cameras[s]) != V:
-                    raise capi.FvpError(f"cameras holds no {V} cameras for sequence {s!r}")
-                rows = np.stack([HotPath._cam_row(cameras[s][c]) for c in range(V)])
-                t = torch.from_numpy(rows).to(device)[None]
-                self._cams = t if self._cams is None else torch.cat([self._cams, t], dim=0)
-                self._seq_ids[s] = self._cams.shape[0] - 1
-                self._frame_sets.clear()
-        if seqs not in self._frame_sets:
-            if len(self._frame_sets) >= 256:            # bounded, as in the engine
-                self._frame_sets.pop(next(iter(self._frame_sets)))
-            self._frame_sets[seqs] = torch.tensor([self._seq_ids[s] for s in seqs], dtype=torch.int32, device=device)
-        return self._cams, self._frame_sets[seqs]
+        self._cameras = CameraTables()                 # of the sequences handed in as camera dicts
+        self._seq_ids = self._cameras.ids
 
     def __call__(self, fused_poses, cameras_or_cams, frame_set_or_meta, views=None, ids=None, frame_size=None):
         """``fused_poses [B,N,J,5]`` (the forward's, a smoother's, ground truth) -> ``(occluder [B,V,N,J] int32, vis_conf
@@ -115,46 +92,20 @@ class JointVisibility:
         (``meta['seq']`` names the sequence of each frame; a sequence's cameras are uploaded when it is first seen, V is
         then taken from ``views`` or the dict).  ``ids [B,N]`` int32 (``last_tracks[0]``): a slot with a negative id is
         neither evaluated nor an occluder.  One launch on the current stream."""
-        p = fused_poses
-        if not torch.is_tensor(p) or p.dtype != torch.float32 or p.dim() != 4 or tuple(p.shape[2:]) != (self.J, 5) \
-                or not p.is_contiguous():
-            raise capi.FvpError(f"fused_poses must be a contiguous float32 tensor [B,N,{self.J},5], got "
-                                f"{getattr(p, 'dtype', type(p))} {tuple(getattr(p, 'shape', ()))}")
-        if not self._injected and p.device.type != "cuda":
-            raise capi.FvpError(f"fused_poses live on {p.device}: the visibility test runs on a ROCm GPU device (spelled "
-                                "'cuda:N' in PyTorch-ROCm); there is no CPU fallback")
+        p = tensor_arg("fused_poses", fused_poses, torch.float32, ("B", "N", self.J, 5))
+        require_gpu("the visibility test", p.device, self._injected)
         B, N = p.shape[:2]
-        v = views
-        if v is not None and (not torch.is_tensor(v) or v.dtype != torch.float32 or v.device != p.device or v.dim() != 5
-                              or v.shape[0] != B or tuple(v.shape[2:]) != (N, self.J, 4) or not v.is_contiguous()):
-            raise capi.FvpError(f"views must be a contiguous float32 tensor [{B},V,{N},{self.J},4] on {p.device} (what "
-                                f"joint_evidence returns), got {getattr(v, 'dtype', type(v))} {tuple(getattr(v, 'shape', ()))}")
-        if torch.is_tensor(cameras_or_cams):
-            cams, fs = cameras_or_cams, frame_set_or_meta
-            if cams.dtype != torch.float32 or cams.device != p.device or cams.dim() != 3 or cams.shape[0] < 1 \
-                    or cams.shape[2] != capi.FVP_CAM_FLOATS or not cams.is_contiguous():
-                raise capi.FvpError(f"cams must be a contiguous float32 tensor [nsets,V,{capi.FVP_CAM_FLOATS}] on {p.device}, "
-                                    f"got {cams.dtype} {tuple(cams.shape)}")
-            if not torch.is_tensor(fs) or fs.dtype != torch.int32 or fs.device != p.device or tuple(fs.shape) != (B,) \
-                    or not fs.is_contiguous():
-                raise capi.FvpError(f"with a cams tensor, the frames' camera sets must be a contiguous int32 tensor [{B}] on "
-                                    f"{p.device}")
-            V = cams.shape[1]
-        else:
-            seqs = frame_set_or_meta["seq"] if isinstance(frame_set_or_meta, dict) else frame_set_or_meta
-            if len(seqs) != B:
-                raise capi.FvpError(f"{len(seqs)} sequence names for {B} frames")
-            V = v.shape[1] if v is not None else (len(cameras_or_cams[seqs[0]]) if B else 1)
-            cams, fs = self._tables(cameras_or_cams, seqs, V, p.device)
+        v = tensor_arg("views", views, torch.float32, (B, "V", N, self.J, 4), p.device, hint="what joint_evidence returns",
+                       optional=True)
+        # a cameras dict says nothing about V: the views do, else the dict's first sequence
+        known_V = v.shape[1] if v is not None and not torch.is_tensor(cameras_or_cams) else None
+        cams, fs, V = resolve_cameras(self._cameras, cameras_or_cams, frame_set_or_meta, B, known_V, p.device)
         if v is not None and v.shape[1] != V:
             raise capi.FvpError(f"views hold {v.shape[1]} views, the camera table {V}")
         if not 1 <= N <= MAX_PEOPLE or not 1 <= V <= capi.FVP_MAX_VIEWS:
             raise capi.FvpError(f"JointVisibility limits: 1 <= N <= {MAX_PEOPLE}, 1 <= V <= {capi.FVP_MAX_VIEWS} (N = {N}, "
                                 f"V = {V})")
-        if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != p.device
-                                or tuple(ids.shape) != (B, N) or not ids.is_contiguous()):
-            raise capi.FvpError(f"ids must be a contiguous int32 tensor [{B},{N}] on {p.device} (what PoseTracker.update "
-                                "returns)")
+        tensor_arg("ids", ids, torch.int32, (B, N), p.device, hint="what PoseTracker.update returns", optional=True)
         Hs, Ws = 1, 1
         if v is not None:
             size = self.frame_size if frame_size is None else frame_size
@@ -171,7 +122,7 @@ class JointVisibility:
             vis_count = torch.empty((B, N, self.J), dtype=torch.int32, device=p.device)
         if B == 0:
             return occluder, vis_conf, vis_count        # all empty (an empty tensor has no address to pass)
-        stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream) if p.device.type == "cuda" else None
+        stream = stream_ptr(p.device)
         rc = self.lib.fvp_joint_visibility(_ptr(p), _ptr(cams), _ptr(fs), _ptr(ids), _ptr(v), B, V, N, self.J, self._prims,
                                            self._radius, len(self.prims), self.guard, Hs, Ws, _ptr(occluder), _ptr(vis_conf),
                                            _ptr(vis_count), stream)

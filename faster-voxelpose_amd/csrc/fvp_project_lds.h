@@ -51,6 +51,21 @@ struct TapL {      // tap descriptor of one (voxel, view), relative to the stage
   float w[4];      // bilinear weights, ZERO for taps outside the image (0 * pixel = +0: the reference's zero padding)
 };
 
+// The un-staged forms (k_project_triplane_blk / _own) mark a (voxel, view) that CONTRIBUTES NOTHING - the voxel lies outside
+// the person's window, or none of its four taps lies in the image (tap_origin's inside == 0) - with a negative base, and
+// their sampling passes issue neither the four loads nor the FMAs for it (a real base is a float offset into a view's plane,
+// >= 0; the sign rides in a word the quad broadcast carries anyway: no register, no DPP move added).  The predicate is the
+// same in the four lanes of a voxel; lanes that are off issue no request, and a wave whose 16 voxels are all off branches
+// over the pass.
+// Same bits: all four weights of such a sample are zero, so for finite pixels it would have added
+// ((p0 * 0 + p1 * 0) + p2 * 0) + p3 * 0 = +-0 to its accumulator.  An accumulator starts at +0 and is only ever the result of
+// an addition to it, and a sum of two IEEE numbers is -0 only when both are -0: no accumulator is ever -0, and x + (+-0) == x
+// for every other x (+0 + -0 = +0).  The view sums, hence the mean, the clamp and the maxima, keep every bit.
+// Non-finite pixels: 0 * inf used to put a NaN into the sum; skipped, they are not read at all, which is what the reference's
+// grid_sample zero padding does.  Samples with only some taps outside are untouched: four loads, zero weights.
+constexpr int kTapSkip = -1;
+__device__ __forceinline__ bool tap_contributes(const TapL& t) { return t.base >= 0; }
+
 template <int SRC>
 __device__ __forceinline__ TapL quad_bcast_l(const TapL& t) {
   TapL r;
@@ -77,6 +92,13 @@ __device__ __forceinline__ void tap_origin(float gx, float gy, int W, int H, int
   const bool x0in = x0 >= 0 && x0 < W, x1in = x0 + 1 >= 0 && x0 + 1 < W;
   const bool y0in = y0 >= 0 && y0 < H, y1in = y0 + 1 >= 0 && y0 + 1 < H;
   inside = (x0in && y0in ? 1 : 0) | (x1in && y0in ? 2 : 0) | (x0in && y1in ? 4 : 0) | (x1in && y1in ? 8 : 0);
+}
+
+// -1 where tap_origin's inside == 0, else 0, from the nw pixel alone: some tap column is in the image iff x0 is in
+// [-1, W - 1], some tap row iff y0 is in [-1, H - 1]; one of the four differences is negative otherwise.  Plain integer
+// VALU on purpose: as compares the test holds scalar register pairs that the uncached 20-channel forms do not have.
+__device__ __forceinline__ int tap_skip_mask(int x0, int y0, int W, int H) {
+  return ((x0 + 1) | (W - 1 - x0) | (y0 + 1) | (H - 1 - y0)) >> 31;
 }
 
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
@@ -472,6 +494,9 @@ k_project_triplane_lds(const float* __restrict__ heat_cl, const Cam* __restrict_
 // 4 x 4 x 16 346-352 us (339-341 us on the boxes of profiles/triplane_owned.txt, where the owned form below, which the
 // shipped library launches instead wherever its cells fit, takes 327-329 us).  Ablations of the 8 x 4 x 32 form: 395 us = 247 us sampling (10.5 GB of 64-byte taps: the L1's
 // 64 B/clk/CU line rate gives 268 us) + 81 us plane maxima + 67 us coordinates / tap descriptors.
+// All of these figures were taken while EVERY (voxel, view) issued its four loads.  Since samples that cannot contribute are
+// skipped (kTapSkip above; profiles/projection_skip_oob.txt) 21.5 % of the benchmark's in-window samples fetch nothing and the
+// owned form takes 281-283 us per launch against 325-328 (Shelf 458 -> 421, Campus 143 -> 136): 18 % of the 247 us of sampling.
 #ifndef FVP_TRI_BLK_BZ
 #define FVP_TRI_BLK_BZ 16
 #endif
@@ -549,6 +574,10 @@ k_project_triplane_blk(const float* __restrict__ heat_cl, const Cam* __restrict_
   float* pyz = planes + (size_t(p) * 3 + 2) * J * CC;
   const float nv = float(V);
   const int JPp = JP + 1;                                                // cell pitch (see below)
+  // -1 where the lane's LAST quad group (channels 16 (NVL - 1) + 4 q ...) lies beyond JP, else 0; the groups before it are
+  // below JP for every lane (NVL = ceil(JP / 16)).  Kept as an integer beside the tap's sign (kTapSkip) so that one compare
+  // decides a sampling pass: as a lane mask it is one more scalar pair held across the loops.
+  const int chend = (JP - 1 - (16 * (NVL - 1) + 4 * q)) >> 31;
   [[maybe_unused]] int mxy[NVL][4];                                      // ZRES: running x-y maxima of this lane's column
   [[maybe_unused]] const int zt = 1 << zsh;
   if constexpr (ZRES) {
@@ -592,7 +621,8 @@ k_project_triplane_blk(const float* __restrict__ heat_cl, const Cam* __restrict_
         const int gzi = gz0 + zs + 4 * (q + 4 * k);
         const bool vin = col_in && gzi < e2;
         TapL d;
-        d.base = d.dx = d.dy = 0;
+        d.base = kTapSkip;                                 // outside the window: contributes nothing
+        d.dx = d.dy = 0;
         d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0.0f;
         if (vin) {
           float sx, sy;
@@ -607,7 +637,7 @@ k_project_triplane_blk(const float* __restrict__ heat_cl, const Cam* __restrict_
           tap_origin(sx, sy, W, H, x0, y0, w4, inside);
           const int cx0 = imin(imax(x0, 0), W - 1), cx1 = imin(imax(x0 + 1, 0), W - 1);
           const int cy0 = imin(imax(y0, 0), H - 1), cy1 = imin(imax(y0 + 1, 0), H - 1);
-          d.base = (cy0 * W + cx0) * JP;
+          d.base = ((cy0 * W + cx0) * JP) | tap_skip_mask(x0, y0, W, H);   // kTapSkip: no tap in the image
           d.dx = (cx1 - cx0) * JP;
           d.dy = (cy1 - cy0) * W * JP;
 #pragma unroll
@@ -625,7 +655,7 @@ k_project_triplane_blk(const float* __restrict__ heat_cl, const Cam* __restrict_
 #pragma unroll
         for (int n = 0; n < (kOwn ? 1 : NVA); ++n) {
           const int ch0 = kOwn ? 16 : 16 * n + 4 * q;
-          if (kOwn || ch0 < JP) {
+          if (((kOwn || n + 1 < NVL ? 0 : chend) | tv.base) >= 0) {       // the lane has these channels and the sample contributes
             const float* p0 = gsrc + tv.base + ch0;
             const float4 v0 = glb_ld4(p0), v1 = glb_ld4(p0 + tv.dx), v2 = glb_ld4(p0 + tv.dy), v3 = glb_ld4(p0 + tv.dy + tv.dx);
             const f32x2 w0 = f32x2{tv.w[0], tv.w[0]}, w1 = f32x2{tv.w[1], tv.w[1]}, w2 = f32x2{tv.w[2], tv.w[2]},
@@ -980,7 +1010,8 @@ k_project_triplane_own(const float* __restrict__ heat_cl, const Cam* __restrict_
           const int gzi = gz0 + zs + 4 * (q + 4 * k);
           const bool vin = col_in && gzi < e2;
           TapL d;
-          d.base = d.dx = d.dy = 0;
+          d.base = kTapSkip;                                 // outside the window: contributes nothing
+          d.dx = d.dy = 0;
           d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0.0f;
           if (vin) {
             float sx, sy;
@@ -995,7 +1026,7 @@ k_project_triplane_own(const float* __restrict__ heat_cl, const Cam* __restrict_
             tap_origin(sx, sy, W, H, x0, y0, w4, inside);
             const int cx0 = imin(imax(x0, 0), W - 1), cx1 = imin(imax(x0 + 1, 0), W - 1);
             const int cy0 = imin(imax(y0, 0), H - 1), cy1 = imin(imax(y0 + 1, 0), H - 1);
-            d.base = (cy0 * W + cx0) * JP;
+            d.base = ((cy0 * W + cx0) * JP) | tap_skip_mask(x0, y0, W, H);   // kTapSkip: no tap in the image
             d.dx = (cx1 - cx0) * JP;
             d.dy = (cy1 - cy0) * W * JP;
 #pragma unroll
@@ -1010,7 +1041,9 @@ k_project_triplane_own(const float* __restrict__ heat_cl, const Cam* __restrict_
 #pragma unroll
           for (int n = 0; n < (kOwn ? 1 : NVA); ++n) {
             const int ch0 = kOwn ? 16 : 16 * n + 4 * q;
-            if (kOwn || ch0 < JP) {
+            // (only a lane's last quad group can lie beyond JP: NVL = ceil(JP / 16).  The block form folds that test into the
+            // sign as well; here that form costs four VGPRs in the 24-32 channel kernels, this one none)
+            if ((kOwn || n + 1 < NVL || ch0 < JP) && tap_contributes(tv)) {
               const float* p0 = gsrc + tv.base + ch0;
               const float4 v0 = glb_ld4(p0), v1 = glb_ld4(p0 + tv.dx), v2 = glb_ld4(p0 + tv.dy), v3 = glb_ld4(p0 + tv.dy + tv.dx);
               const f32x2 w0 = f32x2{tv.w[0], tv.w[0]}, w1 = f32x2{tv.w[1], tv.w[1]}, w2 = f32x2{tv.w[2], tv.w[2]},

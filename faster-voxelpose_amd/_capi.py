@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 19           # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 20          # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -17,6 +17,11 @@ FVP_MAX_VIEWS = 8
 FVP_MAX_JOINTS = 32
 FVP_TRACK_MAX_DETS = 32
 FVP_TRACK_MAX_TRACKS = 64
+FVP_SIG_MAX_PARTS = 4
+FVP_SIG_BINS = 64
+FVP_SIG_MAX_SAMPLES = 16384
+FVP_REID_MAX_GALLERY = 64
+FVP_REID_MAX_WINDOW = 1024
 FVP_VIS_MAX_PEOPLE = 32
 FVP_VIS_MAX_PRIMS = 64
 FVP_TRI_MAX_RADIUS = 8
@@ -83,6 +88,9 @@ SIGNATURES = {
     "fvp_joint_evidence": [_P, _P, _P, _P, _I, _I, _G, _P, _P, _P],
     "fvp_track_update": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "fvp_track_smooth": [_P] * 12 + [_I] * 5 + [_F] * 6 + [_I, _P],
+    "fvp_person_signature": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I,
+                             _I, _F, _P, _P, _P],
+    "fvp_track_reid": [_P] * 17 + [_I] * 10 + [_F, _F, _I, _P],
     "fvp_zmax": [_P, _P, C.c_long, _I, _P],
     "fvp_person_boxes": [_P, _I, _P, _P, _P, _P, _P],
     "fvp_project_individual": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _G, _P, _P],

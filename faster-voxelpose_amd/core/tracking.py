@@ -7,6 +7,7 @@ sequence - nearest-pose greedy association with a distance gate, births, a maxim
 defined bit for bit in include/fvp.h.  Pose smoothing and coasting through gaps consume the ids: core/smoothing.py
 (``PoseSmoother``).  Not built: motion prediction inside the association (it runs on the raw last pose, not on the smoother's
 predictions), re-identification after ``max_age``, Hungarian (optimal) assignment.
+Re-identification of a person who comes back after ``max_age`` is ``fvp_track_reid``: core/reid.py (``PersonReId``).
 
 No arithmetic happens here and nothing synchronises with the host: PyTorch is used for device memory and streams only.
 """

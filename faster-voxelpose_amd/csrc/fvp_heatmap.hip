@@ -649,6 +649,73 @@ k_crop_rois_nv12(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp
   });
 }
 
+// ---- person signature (fvp_person_signature; include/fvp.h, ABI 20) -------------------------------------------------------
+// A colour histogram per person and body part from the frame pixels under the person's limbs.  One workgroup per (b, n): item
+// (v, l, m) - sample m of limb l in view v - is strided over the threads, each tests its limb's two joints (draw_joint's
+// compares, restated on the floats, and the occluder table), interpolates, rounds and reads ONE pixel; the P x 64 counters sit
+// in LDS behind integer atomics, so the result does not depend on the order, and go out coalesced.  V * L * K <= 16384 items of
+// a few dependent loads each: latency-bound, nothing is tuned.  The limb tables are kernel arguments (SGPRs / the kernarg
+// segment), as the overlay's are; no per-thread array exists, so nothing can become scratch.
+struct SigPrm {
+  uint8_t limb[64][2];
+  uint8_t part[64];
+};
+constexpr int kSigThreads = 256, kSigMaxL = 64, kSigMaxK = 32;
+
+__device__ __forceinline__ bool sig_joint(const float* __restrict__ views, const float* __restrict__ conf,
+                                          const int32_t* __restrict__ occ, float conf_min, long vj, long cj, float& px,
+                                          float& py) {
+  px = views[4 * vj];
+  py = views[4 * vj + 1];
+  bool ok = views[4 * vj + 2] > 0.0f && fabsf(px) <= 32768.0f && fabsf(py) <= 32768.0f;
+  if (conf) ok = ok && conf[cj] >= conf_min;
+  if (occ) ok = ok && occ[vj] == -1;
+  return ok;
+}
+
+__global__ void __launch_bounds__(kSigThreads)
+k_person_signature(const uint8_t* __restrict__ frames, int V, int Hs, int Ws, const float* __restrict__ views,
+                   const int32_t* __restrict__ ids, const float* __restrict__ conf, const int32_t* __restrict__ occ, int N,
+                   int J, int L, int P, int K, SigPrm prm, float conf_min, int32_t* __restrict__ sig,
+                   int32_t* __restrict__ sig_count) {
+  __shared__ int s_hist[FVP_SIG_MAX_PARTS * FVP_SIG_BINS];
+  const int bn = blockIdx.x, b = bn / N, n = bn - b * N, tid = threadIdx.x;
+  const int cells = P * FVP_SIG_BINS;
+  if (tid < cells) s_hist[tid] = 0;                      // cells <= kSigThreads
+  __syncthreads();
+  if (!ids || ids[bn] >= 0) {                            // uniform over the workgroup
+    const int LK = L * K, items = V * LK;
+    const float fK = float(K);
+    const long crow = long(bn) * J;
+#pragma unroll 1
+    for (int it = tid; it < items; it += kSigThreads) {
+      const int v = it / LK, r = it - v * LK, l = r / K, m = r - l * K;
+      const long f = long(b) * V + v, vrow = (f * N + n) * J;
+      const int j0 = prm.limb[l][0], j1 = prm.limb[l][1];
+      float ax, ay, bx, by;
+      const bool ok0 = sig_joint(views, conf, occ, conf_min, vrow + j0, crow + j0, ax, ay);
+      const bool ok1 = sig_joint(views, conf, occ, conf_min, vrow + j1, crow + j1, bx, by);
+      if (!(ok0 && ok1)) continue;
+      const float t = __fdiv_rn(__fadd_rn(float(m), 0.5f), fK);
+      const float x = __fadd_rn(ax, __fmul_rn(t, __fsub_rn(bx, ax))), y = __fadd_rn(ay, __fmul_rn(t, __fsub_rn(by, ay)));
+      const int xi = int(rintf(x)), yi = int(rintf(y));  // |x|, |y| <= 32768: the conversion is exact; round-half-even
+      if (xi < 0 || xi >= Ws || yi < 0 || yi >= Hs) continue;
+      const uint8_t* p = frames + ((f * Hs + yi) * Ws + xi) * 3;
+      draw_note_read(p);
+      const int bin = (p[0] >> 6) * 16 + (p[1] >> 6) * 4 + (p[2] >> 6);
+      atomicAdd(&s_hist[prm.part[l] * FVP_SIG_BINS + bin], 1);
+    }
+  }
+  __syncthreads();
+  if (sig && tid < cells) sig[long(bn) * cells + tid] = s_hist[tid];
+  if (sig_count && tid < P) {
+    int c = 0;
+#pragma unroll 1
+    for (int i = 0; i < FVP_SIG_BINS; ++i) c += s_hist[tid * FVP_SIG_BINS + i];
+    sig_count[long(bn) * P + tid] = c;
+  }
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -871,5 +938,31 @@ extern "C" int fvp_crop_rois_nv12(const uint8_t* y, const uint8_t* uv, int F, in
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_crop_rois_nv12, dim3(unsigned(R), unsigned(blocks)), dim3(256), 0, as_stream(s), y, uv, Hs, Ws, q,
                      rois, rois_per_frame, nm, h, w, nhwc8, nchw);
+  return launch_status();
+}
+
+extern "C" int fvp_person_signature(const uint8_t* frames, int B, int V, int Hs, int Ws, const float* views,
+                                    const int32_t* ids, const float* joint_conf, const int32_t* occluder, int N, int J,
+                                    const int32_t* limbs, const int32_t* limb_part, int L, int P, int K, float conf_min,
+                                    int32_t* sig, int32_t* sig_count, fvp_stream_t s) {
+  FVP_REQUIRE(frames && views && limbs && limb_part && (sig || sig_count));
+  FVP_REQUIRE(B >= 0 && V >= 0 && N >= 1 && J >= 1 && Hs >= 1 && Ws >= 1 && L >= 1 && P >= 1);
+  FVP_REQUIRE(K >= 1 && K <= kSigMaxK && !std::isnan(conf_min));
+  FVP_LIMIT(N <= kDrawMaxN && J <= FVP_MAX_JOINTS && V <= FVP_MAX_VIEWS && L <= kSigMaxL && P <= FVP_SIG_MAX_PARTS);
+  FVP_LIMIT(Hs <= 16384 && Ws <= 16384);
+  SigPrm prm = {};
+  for (int l = 0; l < L; ++l) {
+    for (int e = 0; e < 2; ++e) {
+      FVP_REQUIRE(limbs[2 * l + e] >= 0 && limbs[2 * l + e] < J);
+      prm.limb[l][e] = uint8_t(limbs[2 * l + e]);
+    }
+    FVP_REQUIRE(limb_part[l] >= 0 && limb_part[l] < P);
+    prm.part[l] = uint8_t(limb_part[l]);
+  }
+  if (long(B) * V == 0) return 0;
+  FVP_LIMIT(long(B) * N < (1l << 31));                   // one workgroup per (b, n)
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_person_signature, dim3(unsigned(B * N)), dim3(kSigThreads), 0, as_stream(s), frames, V, Hs, Ws, views,
+                     ids, joint_conf, occluder, N, J, L, P, K, prm, conf_min, sig, sig_count);
   return launch_status();
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <cmath>
 
 #include "fvp_common.h"
 
@@ -513,6 +514,271 @@ k_track_smooth(const float* __restrict__ poses, const int* __restrict__ frame_se
   }
 }
 
+// ---- person re-identification (ABI 20): a gallery of retired tracks per sequence -----------------------------------------
+// The definition is in include/fvp.h.  One workgroup of 256 threads per sequence walks the batch's frames in order and skips
+// the frames of other sequences, as k_track_update does.  Thread (p, bin) = tid owns counter (p, bin) of EVERY slot and gallery
+// signature of its sequence: accumulating, halving, storing a retired slot in the gallery and clearing are thread-private
+// read-modify-writes of global memory with no hand-over between threads, so the signatures (up to 2 x 64 KB) need no LDS.  A
+// part is a wave (64 bins): its sums Ca, Cg and the int64 intersection are wave reductions over shuffles.  The scalars of the
+// slots and of the gallery live in LDS; every thread reads them and takes the same branches, thread 0 alone writes them.  The
+// slot scalars are double-buffered per frame (read copy `cur`, written copy `cur ^ 1`; every slot is rewritten every frame), so
+// a wave that lags at the start of slot t never sees thread 0's end-of-slot write; the gallery scalars change between two
+// barriers.  Latency-bound: B * T dependent rounds of a few loads, and a decision (G rounds of shuffles) once per track.
+constexpr int kReidThreads = FVP_SIG_MAX_PARTS * FVP_SIG_BINS, kReidGallery = FVP_REID_MAX_GALLERY;
+static_assert(FVP_SIG_BINS == 64, "a wave sums a part");
+
+struct ReidPrm {
+  int max_age, min_samples, min_frames, window, gallery_max_age;
+  float sim_min, margin;
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ long long wave_sum64(long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = unsigned(__shfl_xor(int(v), o)), hi = unsigned(__shfl_xor(int(v >> 32), o));
+    v += (long long)((unsigned long long)hi << 32 | lo);
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(kReidThreads)
+k_track_reid(const int* __restrict__ ids, const int* __restrict__ slots, const int* __restrict__ sig,
+             const int* __restrict__ sig_count, const int* __restrict__ frame_set, int* __restrict__ slot_sig,
+             int* __restrict__ slot_tid, int* __restrict__ slot_pid, int* __restrict__ slot_frames,
+             int* __restrict__ slot_age, float* __restrict__ slot_sim, int* __restrict__ gal_sig, int* __restrict__ gal_pid,
+             int* __restrict__ gal_age, int* __restrict__ pids, int* __restrict__ reid_state, float* __restrict__ reid_sim,
+             int B, int N, int nseq, int T, int G, int P, ReidPrm q) {
+  __shared__ int s_st[2][5][kTrackSlots];                  // slot scalars: tid, pid, frames, age, sim bits
+  __shared__ int s_n[kTrackSlots];                         // the frame's detection of every slot, -1 = none
+  __shared__ int s_gpid[kReidGallery], s_gage[kReidGallery], s_gfreed[kReidGallery];
+  __shared__ long long s_inter[kReidGallery][FVP_SIG_MAX_PARTS];
+  __shared__ int s_cg[kReidGallery][FVP_SIG_MAX_PARTS], s_ca[FVP_SIG_MAX_PARTS];
+  __shared__ float s_sim[kReidGallery];
+  const int s = blockIdx.x, tid = threadIdx.x, p = tid >> 6, lane = tid & 63, cells = P * FVP_SIG_BINS;
+  const bool active = p < P;                               // wave-uniform
+  const int none = __float_as_int(-1.0f);
+  int* ssig = slot_sig + size_t(s) * T * cells + tid;      // this thread's counter of slot t: ssig[t * cells]
+  int* gsig = gal_sig + size_t(s) * G * cells + tid;
+  // The state and output pointers become per-thread addresses in vector registers here, opaque to the optimiser: kept as
+  // seventeen scalar bases they are live from the first load to the last store and the kernel spills scalar registers.
+  int* p_tid = slot_tid + size_t(s) * T + tid;
+  int* p_pid = slot_pid + size_t(s) * T + tid;
+  int* p_frames = slot_frames + size_t(s) * T + tid;
+  int* p_age = slot_age + size_t(s) * T + tid;
+  float* p_sim = slot_sim + size_t(s) * T + tid;
+  int* p_gpid = gal_pid + size_t(s) * G + tid;
+  int* p_gage = gal_age + size_t(s) * G + tid;
+  int* o_pid = pids + tid;
+  int* o_state = reid_state + tid;
+  float* o_sim = reid_sim + tid;
+  FVP_OPAQUE_V(ssig); FVP_OPAQUE_V(gsig); FVP_OPAQUE_V(p_tid); FVP_OPAQUE_V(p_pid); FVP_OPAQUE_V(p_frames);
+  FVP_OPAQUE_V(p_age); FVP_OPAQUE_V(p_sim); FVP_OPAQUE_V(p_gpid); FVP_OPAQUE_V(p_gage);
+  FVP_OPAQUE_V(o_pid); FVP_OPAQUE_V(o_state); FVP_OPAQUE_V(o_sim);
+  const int* v_sig = sig + tid;                            // (the two signature inputs likewise)
+  const int* v_cnt = sig_count;
+  FVP_OPAQUE_V(v_sig); FVP_OPAQUE_V(v_cnt);
+  if (tid < T) {
+    s_st[0][0][tid] = *p_tid;
+    s_st[0][1][tid] = *p_pid;
+    s_st[0][2][tid] = *p_frames;
+    s_st[0][3][tid] = *p_age;
+    s_st[0][4][tid] = __float_as_int(*p_sim);
+  }
+  if (tid < G) {
+    s_gpid[tid] = *p_gpid;
+    s_gage[tid] = *p_gage;
+  }
+  int cur = 0;
+
+#pragma unroll 1
+  for (int b = 0; b < B; ++b) {
+    const int fs = frame_set ? frame_set[b] : 0;
+    if (fs != s) {
+      // a frame of no sequence: nobody owns it, workgroup 0 writes it as all invalid
+      if (s == 0 && (fs < 0 || fs >= nseq) && tid < N) {
+        o_pid[size_t(b) * N] = -1;
+        o_state[size_t(b) * N] = -1;
+        o_sim[size_t(b) * N] = -1.0f;
+      }
+      continue;
+    }
+    const int* fid = ids + size_t(b) * N;
+    const int* fsl = slots + size_t(b) * N;
+    __syncthreads();                                       // the state as loaded / as the previous frame left it
+    if (tid < T) {
+      int first = -1;
+#pragma unroll 1
+      for (int n = N - 1; n >= 0; --n)
+        if (fid[n] >= 0 && fsl[n] == tid) first = n;
+      s_n[tid] = first;
+    }
+    if (tid < G) {                                         // 1. gallery ageing
+      int freed = 0;
+      if (s_gpid[tid] >= 0) {
+        const int age = s_gage[tid] + 1;
+        freed = q.gallery_max_age > 0 && age > q.gallery_max_age;
+        s_gage[tid] = freed ? 0 : age;
+        if (freed) s_gpid[tid] = -1;
+      }
+      s_gfreed[tid] = freed;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int g = 0; g < G; ++g)
+      if (s_gfreed[g] && active) gsig[size_t(g) * cells] = 0;
+
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {                          // 2. the slots in ascending order; every branch is uniform
+      const int n = s_n[t];
+      int id = s_st[cur][0][t], pid = s_st[cur][1][t], frames = s_st[cur][2][t], age = s_st[cur][3][t];
+      int simb = s_st[cur][4][t];
+      const int nid = n >= 0 ? fid[n] : -1;
+      if (id >= 0 && (n >= 0 ? nid != id : age + 1 > q.max_age)) {           // a. retire
+        if (frames >= q.min_frames) {
+          int gsel = -1, oldest = -1, gold = 0;
+#pragma unroll 1
+          for (int g = 0; g < G; ++g) {
+            if (s_gpid[g] < 0) {
+              if (gsel < 0) gsel = g;                                         // the lowest free entry
+            } else if (s_gage[g] > oldest) {                                  // else the largest age, lowest index on a tie
+              oldest = s_gage[g];
+              gold = g;
+            }
+          }
+          if (gsel < 0) gsel = gold;
+          if (active) gsig[size_t(gsel) * cells] = ssig[size_t(t) * cells];
+          __syncthreads();                                 // every thread has scanned the gallery scalars
+          if (tid == 0) {
+            s_gpid[gsel] = pid >= 0 ? pid : id;
+            s_gage[gsel] = 0;
+          }
+          __syncthreads();
+        }
+        if (active) ssig[size_t(t) * cells] = 0;
+        id = -1; pid = -1; frames = 0; age = 0; simb = none;
+      }
+      if (n < 0 && id >= 0) ++age;                                            // b. coast
+      if (n >= 0) {
+        if (id != nid) id = nid;                                              // c. birth: the slot is in the cleared state
+        age = 0;                                                              // d. accumulate
+        int cnt = 0;
+#pragma unroll 1
+        for (int pp = 0; pp < P; ++pp) cnt += v_cnt[(size_t(b) * N + n) * P + pp];
+        if (cnt >= q.min_samples) {
+          if (active) {
+            int a = ssig[size_t(t) * cells];
+            if (frames == q.window) a >>= 1;
+            ssig[size_t(t) * cells] = a + v_sig[(size_t(b) * N + n) * cells];
+          }
+          if (frames == q.window) frames = q.window >> 1;
+          ++frames;
+        }
+      }
+      if (id >= 0 && pid == -1 && frames >= q.min_frames) {                   // e. decide
+        const int a = active ? ssig[size_t(t) * cells] : 0;
+        const int Ca = wave_sum(a);
+        if (lane == 0) s_ca[p] = Ca;
+#pragma unroll 1
+        for (int g = 0; g < G; ++g) {
+          if (s_gpid[g] < 0) continue;
+          const int gv = active ? gsig[size_t(g) * cells] : 0;
+          const int Cg = wave_sum(gv);
+          const long long x = (long long)a * Cg, y = (long long)gv * Ca;
+          const long long inter = wave_sum64(x < y ? x : y);
+          if (lane == 0) {
+            s_inter[g][p] = inter;
+            s_cg[g][p] = Cg;
+          }
+        }
+        __syncthreads();
+        if (tid < G && s_gpid[tid] >= 0) {
+          double acc = 0.0;
+          int parts = 0;
+#pragma unroll 1
+          for (int pp = 0; pp < P; ++pp) {
+            const int ca = s_ca[pp], cg = s_cg[tid][pp];
+            if (ca > 0 && cg > 0) {
+              acc = acc + double(s_inter[tid][pp]) / (double(ca) * double(cg));
+              ++parts;
+            }
+          }
+          s_sim[tid] = parts ? float(acc / double(parts)) : 0.0f;
+        }
+        __syncthreads();
+        int best = -1;
+        float sb = 0.0f, s2 = 0.0f;
+#pragma unroll 1
+        for (int g = 0; g < G; ++g) {
+          if (s_gpid[g] < 0) continue;
+          const float v = s_sim[g];
+          if (best < 0) {
+            best = g;
+            sb = v;
+          } else if (v > sb) {                             // (a tie keeps the lower g)
+            s2 = sb;
+            best = g;
+            sb = v;
+          } else if (v > s2) {
+            s2 = v;
+          }
+        }
+        if (best >= 0 && sb >= q.sim_min && __fsub_rn(sb, s2) >= q.margin) {  // adopt: the entry is freed
+          pid = s_gpid[best];
+          if (active) gsig[size_t(best) * cells] = 0;
+          __syncthreads();                                 // every thread has read the gallery scalars
+          if (tid == 0) {
+            s_gpid[best] = -1;
+            s_gage[best] = 0;
+          }
+          __syncthreads();
+        } else {
+          pid = id;
+        }
+        simb = best >= 0 ? __float_as_int(sb) : none;
+      }
+      if (tid == 0) {
+        s_st[cur ^ 1][0][t] = id;
+        s_st[cur ^ 1][1][t] = pid;
+        s_st[cur ^ 1][2][t] = frames;
+        s_st[cur ^ 1][3][t] = age;
+        s_st[cur ^ 1][4][t] = simb;
+      }
+    }
+    cur ^= 1;
+    __syncthreads();
+    if (tid < N) {                                         // 3. outputs
+      const int t = fsl[tid];
+      int op = -1, os = -1, ob = none;
+      if (fid[tid] >= 0 && t >= 0 && t < T) {
+        const int id = s_st[cur][0][t], pid = s_st[cur][1][t];
+        op = pid >= 0 ? pid : id;
+        os = pid < 0 ? 0 : pid == id ? 1 : 2;
+        ob = s_st[cur][4][t];
+      }
+      o_pid[size_t(b) * N] = op;
+      o_state[size_t(b) * N] = os;
+      o_sim[size_t(b) * N] = __int_as_float(ob);
+    }
+  }
+
+  __syncthreads();
+  if (tid < T) {
+    *p_tid = s_st[cur][0][tid];
+    *p_pid = s_st[cur][1][tid];
+    *p_frames = s_st[cur][2][tid];
+    *p_age = s_st[cur][3][tid];
+    *p_sim = __int_as_float(s_st[cur][4][tid]);
+  }
+  if (tid < G) {
+    *p_gpid = s_gpid[tid];
+    *p_gage = s_gage[tid];
+  }
+}
+
 }  // namespace fvp
 
 using namespace fvp;
@@ -601,5 +867,27 @@ extern "C" int fvp_track_smooth(const float* fused_poses, const int32_t* frame_s
                      fused_poses, frame_set, ids, slots, joint_conf, flt_pose, flt_vel, flt_id, flt_age, smooth,
                      track_poses, track_state, B, N, J, nseq, T, rate_hz, min_cutoff, beta, d_cutoff, conf_min, damp,
                      max_age);
+  return launch_status();
+}
+
+extern "C" int fvp_track_reid(const int32_t* ids, const int32_t* slots, const int32_t* sig, const int32_t* sig_count,
+                              const int32_t* frame_set, int32_t* slot_sig, int32_t* slot_tid, int32_t* slot_pid,
+                              int32_t* slot_frames, int32_t* slot_age, float* slot_sim, int32_t* gal_sig, int32_t* gal_pid,
+                              int32_t* gal_age, int32_t* pids, int32_t* reid_state, float* reid_sim, int B, int N, int nseq,
+                              int T, int G, int P, int max_age, int min_samples, int min_frames, int window, float sim_min,
+                              float margin, int gallery_max_age, fvp_stream_t s) {
+  FVP_REQUIRE(ids && slots && sig && sig_count && slot_sig && slot_tid && slot_pid && slot_frames && slot_age && slot_sim);
+  FVP_REQUIRE(gal_sig && gal_pid && gal_age && pids && reid_state && reid_sim);
+  FVP_REQUIRE(B >= 0 && N > 0 && nseq > 0 && G > 0 && P > 0 && T >= N);
+  FVP_REQUIRE(max_age >= 0 && min_samples >= 0 && gallery_max_age >= 0 && min_frames >= 1 && window >= min_frames);
+  FVP_REQUIRE(!std::isnan(sim_min) && !std::isnan(margin));
+  FVP_LIMIT(N <= kTrackDets && T <= kTrackSlots && G <= kReidGallery && P <= FVP_SIG_MAX_PARTS);
+  FVP_LIMIT(window <= FVP_REID_MAX_WINDOW);
+  if (B == 0) return 0;
+  const ReidPrm q = {max_age, min_samples, min_frames, window, gallery_max_age, sim_min, margin};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_track_reid, dim3(nseq), dim3(kReidThreads), 0, as_stream(s), ids, slots, sig, sig_count, frame_set,
+                     slot_sig, slot_tid, slot_pid, slot_frames, slot_age, slot_sim, gal_sig, gal_pid, gal_age, pids,
+                     reid_state, reid_sim, B, N, nseq, T, G, P, q);
   return launch_status();
 }

@@ -26,13 +26,18 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 19
+#define FVP_ABI_VERSION 20
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
 #define FVP_TRACK_MAX_DETS 32   /* fvp_track_update: person slots per frame (N)   */
 #define FVP_TRACK_MAX_TRACKS 64 /* fvp_track_update: track slots per sequence (T) */
-#define FVP_VIS_MAX_PEOPLE 32   /* fvp_joint_visibility: person slots per frame (N) */
+#define FVP_SIG_MAX_PARTS 4      /* fvp_person_signature, fvp_track_reid: body parts of a signature (P) */
+#define FVP_SIG_BINS 64         /* fvp_person_signature, fvp_track_reid: colour bins per part, 2 bits per channel */
+#define FVP_SIG_MAX_SAMPLES 16384 /* samples of one person in one frame: FVP_MAX_VIEWS * 64 limbs * 32 samples */
+#define FVP_REID_MAX_GALLERY 64 /* fvp_track_reid: gallery entries per sequence (G) */
+#define FVP_REID_MAX_WINDOW 1024 /* fvp_track_reid: frames a signature accumulates before it is halved (window) */
+#define FVP_VIS_MAX_PEOPLE 32  /* fvp_joint_visibility: person slots per frame (N) */
 #define FVP_VIS_MAX_PRIMS 64    /* fvp_joint_visibility: body primitives per person (L) */
 #define FVP_TRI_MAX_RADIUS 8    /* fvp_triangulate_joints: window half-size in heat-map cells */
 /* fvp_triangulate_joints: view_state */
@@ -140,6 +145,7 @@ int fvp_joint_evidence(const float* heat_cl, const float* cams, const int32_t* f
  * launch per batch and without host synchronisation.  Nearest-pose greedy association only: no motion prediction (the
  * poses are smoothed, and tracks coast through gaps, by fvp_track_smooth below, which consumes ids / slots; association
  * itself runs on the raw last pose), no re-identification after max_age, no optimal (Hungarian) assignment.
+ * Re-identification of a person who comes back after max_age is fvp_track_reid below, which consumes ids / slots.
  * State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
  *   trk_pose [nseq][T][J][3] fp32, trk_id [nseq][T] int32 (-1 = free slot), trk_age [nseq][T] int32, next_id [nseq] int32;
  *   the initial state is all ids -1, all ages 0, next_id 0 (the poses of free slots are never read).
@@ -216,6 +222,114 @@ int fvp_track_smooth(const float* fused_poses, const int32_t* frame_set, const i
                      int32_t* track_state /* [B,T,2] */, int B, int N, int J, int nseq, int T, float rate_hz,
                      float min_cutoff, float beta, float d_cutoff, float conf_min, float damp, int max_age,
                      fvp_stream_t s);
+
+/* ---- person re-identification (ABI 20): old identities back after a gap -------------------------------------------------
+ * fvp_track_update forgets a track after max_age frames: a person who leaves the capture volume, stays hidden for longer, or
+ * re-appears further than gate_mm from where they vanished comes back under a new track id.  The two calls below give every
+ * track a PERSON id that survives such gaps: fvp_person_signature reads a colour signature of every person from the camera
+ * frames, fvp_track_reid keeps the signatures of retired tracks in a gallery per sequence and hands an old person id to a new
+ * track that looks the same.  A person id is the track id of the first track that person ever had: there is no second
+ * counter.  One launch each, on the device, no host synchronisation.  Everything below is integer arithmetic except where
+ * fp32 / fp64 is named, so no result depends on the order of accumulation or on scheduling.
+ *
+ * fvp_person_signature.  frames [B*V][Hs][Ws][3] uint8: the contiguous HWC layout of fvp_ingest_frames; the three bytes of a
+ * pixel are taken in memory order (c0, c1, c2), there is no channel flag.  views [B][V][N][J][4], ids [B][N] or NULL, joint_conf
+ * [B][N][J] or NULL and conf_min are those of fvp_draw_poses; occluder [B][V][N][J] int32 of fvp_joint_visibility, or NULL.
+ * Body model, HOST memory, passed to the kernel by value: limbs [L][2] int32 joint index pairs, limb_part [L] int32 with values in
+ * [0, P): the body part (for example 0 = upper body, 1 = legs) a limb's samples are counted in; K samples per limb.
+ * Usable joint-view (b,v,n,j): the joint is drawable by fvp_draw_poses' rule - depth > 0, |px| <= 32768 and |py| <= 32768 (fp32
+ *   compares: a NaN or an Inf fails them), joint_conf NULL or joint_conf[b][n][j] >= conf_min (a NaN confidence is not usable) -
+ *   and occluder is NULL or occluder[b][v][n][j] == -1.
+ * Selected person: ids is NULL or ids[b][n] >= 0.
+ * Samples of a selected person (b,n): for every view v, every limb l = (i,k) whose two joints are usable in view v, and m = 0 ..
+ *   K-1, in fp32, every operation rounded on its own (no contraction), IEEE division:
+ *     t = (float(m) + 0.5f) / float(K)
+ *     x = px_i + t * (px_k - px_i)            y = py_i + t * (py_k - py_i)
+ *     xi = (int)rintf(x)                      yi = (int)rintf(y)               round-half-even
+ *   The sample COUNTS iff 0 <= xi < Ws and 0 <= yi < Hs.  Its bin is (c0 >> 6) * 16 + (c1 >> 6) * 4 + (c2 >> 6) of the three
+ *   bytes of pixel (xi, yi) of frame b*V + v.  No byte of a sample that does not count is read, and no byte outside the frames.
+ *   A limb whose two ends coincide puts its K samples on one pixel; they count K times.
+ * Outputs, every element of a non-NULL output written by every call; either may be NULL, not both:
+ *     sig       [B][N][P][FVP_SIG_BINS] int32: the number of counting samples of part limb_part[l] with that bin, over all views
+ *                                              and limbs;
+ *     sig_count [B][N][P]               int32: their sum over the bins (<= FVP_SIG_MAX_SAMPLES over the parts of one person).
+ *   A person that is not selected writes zeros, and so does an invalid slot: fvp_joint_evidence writes its depth as 0.
+ * FVP_EINVAL: null frames, views, limbs or limb_part; both outputs null; B or V < 0; N, J, Hs, Ws, L or P < 1; K outside [1, 32];
+ * a limb index outside [0, J); a part outside [0, P); NaN conf_min.  FVP_ELIMIT: N > 32, J > FVP_MAX_JOINTS, V > FVP_MAX_VIEWS,
+ * L > 64, P > FVP_SIG_MAX_PARTS, Hs or Ws > 16384.  Nothing is written when an error is returned.  B * V == 0 returns 0 without a
+ * launch.  One workgroup per (b, n): the V * L * K samples are strided over its threads, the histogram is built in LDS with
+ * integer atomics and written out coalesced.  Not built: NV12 surfaces, pitched frames, a channel-order flag, learned embeddings. */
+int fvp_person_signature(const uint8_t* frames /* [B*V][Hs][Ws][3] */, int B, int V, int Hs, int Ws,
+                         const float* views /* [B][V][N][J][4] of fvp_joint_evidence */,
+                         const int32_t* ids /* [B][N] or NULL */, const float* joint_conf /* [B][N][J] or NULL */,
+                         const int32_t* occluder /* [B][V][N][J] of fvp_joint_visibility, or NULL */, int N, int J,
+                         const int32_t* limbs /* HOST [L][2] */, const int32_t* limb_part /* HOST [L] */, int L, int P, int K,
+                         float conf_min, int32_t* sig /* [B][N][P][FVP_SIG_BINS] */, int32_t* sig_count /* [B][N][P] */,
+                         fvp_stream_t s);
+
+/* fvp_track_reid.  State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
+ *   slot_sig [nseq][T][P][FVP_SIG_BINS] int32: the signature a track has accumulated;
+ *   slot_tid [nseq][T] int32: the track id the slot's accumulation belongs to, -1 = free;
+ *   slot_pid [nseq][T] int32: the decided person id, -1 = pending;
+ *   slot_frames [nseq][T] int32: frames accumulated;   slot_age [nseq][T] int32: frames since the track was last seen;
+ *   slot_sim [nseq][T] fp32: sim(best) of the slot's decision, -1 before it and when the gallery was empty;
+ *   gal_sig [nseq][G][P][FVP_SIG_BINS] int32, gal_pid [nseq][G] int32 (-1 = free), gal_age [nseq][G] int32: the gallery.
+ *   The initial state is all ids -1, slot_sim -1 and everything else 0.  A free slot and a free gallery entry are always in that
+ *   state: whatever frees one CLEARS it (ids -1, slot_sim -1, every other value and every counter 0).
+ * Inputs per call: ids [B][N] and slots [B][N] as fvp_track_update wrote them for the same batch; sig [B][N][P][FVP_SIG_BINS] and
+ * sig_count [B][N][P] as fvp_person_signature wrote them (counters >= 0, at most FVP_SIG_MAX_SAMPLES per person and frame: with
+ * other values the integer arithmetic below wraps); frame_set [B] (NULL = sequence 0).
+ * Parameters: max_age (the tracker's own), min_samples, min_frames >= 1, window >= min_frames, sim_min, margin (fp32),
+ * gallery_max_age (0 = never forget).  With window <= FVP_REID_MAX_WINDOW no counter passes (window + 1) * FVP_SIG_MAX_SAMPLES
+ * < 2^25, far below 2^30, and every product below is < 2^50: exact in int64 and in fp64.
+ * Frames are consumed in batch order, sequences are independent.  A frame whose frame_set entry is outside [0, nseq) changes
+ * no state and its outputs are written as invalid.  For frame b of sequence s, in this order:
+ *   1. Gallery ageing: every occupied entry (gal_pid >= 0) gets gal_age += 1; with gallery_max_age > 0 an entry whose age is now
+ *      > gallery_max_age is freed.
+ *   2. Every track slot t in ascending t.  n = the lowest detection slot with ids[b][n] >= 0 and slots[b][n] == t, if any
+ *      (fvp_track_smooth's rule: a detection whose slots entry is outside [0, T) is treated like one with ids < 0 everywhere).
+ *      a. RETIRE iff slot_tid[t] >= 0 and either (n exists and ids[b][n] != slot_tid[t]) or (no n and slot_age[t] + 1 > max_age).
+ *         If slot_frames[t] >= min_frames, the pair (slot_pid[t] if it is >= 0, else slot_tid[t]; slot_sig[t]) is stored with
+ *         gal_age = 0 in the lowest free gallery entry or, when none is free, in the entry with the largest gal_age (lowest
+ *         index on a tie), whose former content is lost.  A track with fewer frames is forgotten.  The slot is then cleared.
+ *      b. COAST iff no n and slot_tid[t] >= 0 (still live): slot_age += 1.
+ *      c. BIRTH iff n exists and slot_tid[t] != ids[b][n]: slot_tid = ids[b][n]; the rest of the slot is in the cleared state.
+ *      d. ACCUMULATE iff n exists: slot_age = 0; and if sig_count[b][n][0] + ... + sig_count[b][n][P-1] >= min_samples (int32):
+ *         if slot_frames == window, every counter of slot_sig[t] is first halved (>> 1) and slot_frames = window >> 1 (this bounds
+ *         the counters and lets a signature follow slow lighting changes); then slot_sig[t] += sig[b][n], slot_frames += 1.
+ *      e. DECIDE iff slot_tid[t] >= 0, slot_pid[t] == -1 and slot_frames[t] >= min_frames.  For every occupied gallery entry g:
+ *           for every part p: Ca, Cg = the sum of the slot's, the entry's counters of part p over the bins; the part COUNTS iff
+ *           Ca > 0 and Cg > 0; inter_p = the sum over the bins of min(a_bin * Cg, g_bin * Ca), in int64 (exact);
+ *           sim(g) = float((q_0 + q_1 + ...) / double(parts that count)), q_p = double(inter_p) / (double(Ca) * double(Cg)) over
+ *           the parts that count in ascending p, in fp64, every operation rounded on its own, one rounding to fp32 at the end;
+ *           sim(g) = 0.0f when no part counts.  It is the histogram intersection of the two normalised signatures, in [0, 1].
+ *         best = the occupied entry with the largest sim (lowest g on a tie); second = the largest sim among the other occupied
+ *         entries, 0.0f when there is none.  ADOPT iff a best exists and sim(best) >= sim_min and sim(best) - second >= margin
+ *         (fp32 subtraction and compares: a NaN fails): slot_pid = gal_pid[best] and the entry is freed.  Otherwise slot_pid =
+ *         slot_tid: a new person.  slot_sim = sim(best), or -1.0f when the gallery was empty.
+ *         Slots decide in ascending t, so two pending tracks cannot adopt the same entry: the lower slot takes it.
+ *   3. Outputs, every element written by every call.  Detection n is VALID iff ids[b][n] >= 0 and t = slots[b][n] is in [0, T):
+ *        pids [B][N] int32:       slot_pid[t], or slot_tid[t] while the slot is pending;
+ *        reid_state [B][N] int32: 0 pending, 1 a new person (slot_pid == slot_tid), 2 re-identified (slot_pid != slot_tid);
+ *        reid_sim [B][N] fp32:    slot_sim[t];
+ *      all after step 2 of this frame.  An invalid detection writes -1, -1, -1.0f.
+ * Consequences (tested): with the tracker's own max_age, slot_tid == trk_id in every live slot after every call; a person id is
+ * held by at most one live slot or gallery entry of a sequence at any time; splitting a batch into chunks changes nothing.
+ * The defaults the host class suggests (min_samples, min_frames, window, sim_min, margin) are guesses: nothing was tuned on
+ * real footage.  pids are not fed back into the tracker's association.
+ * FVP_EINVAL: a null pointer (frame_set excepted); B < 0; N, nseq, G or P < 1; T < N; max_age, min_samples or gallery_max_age
+ * < 0; min_frames < 1; window < min_frames; NaN sim_min or margin.  FVP_ELIMIT: N > FVP_TRACK_MAX_DETS, T >
+ * FVP_TRACK_MAX_TRACKS, G > FVP_REID_MAX_GALLERY, P > FVP_SIG_MAX_PARTS, window > FVP_REID_MAX_WINDOW.  Nothing is written when
+ * an error is returned.  B == 0 returns 0 without a launch.  One workgroup per sequence walks the batch: thread (p, bin) owns that
+ * counter of every slot and gallery entry, a wave sums a part.  Not built: re-identification across sequences, learned
+ * embeddings, NV12 surfaces, merging a returning track's gallery signature into its new accumulation. */
+int fvp_track_reid(const int32_t* ids /* [B][N] */, const int32_t* slots /* [B][N] */,
+                   const int32_t* sig /* [B][N][P][FVP_SIG_BINS] */, const int32_t* sig_count /* [B][N][P] */,
+                   const int32_t* frame_set /* [B] or NULL */, int32_t* slot_sig, int32_t* slot_tid, int32_t* slot_pid,
+                   int32_t* slot_frames, int32_t* slot_age, float* slot_sim, int32_t* gal_sig, int32_t* gal_pid,
+                   int32_t* gal_age, int32_t* pids /* [B][N] */, int32_t* reid_state /* [B][N] */,
+                   float* reid_sim /* [B][N] */, int B, int N, int nseq, int T, int G, int P, int max_age, int min_samples,
+                   int min_frames, int window, float sim_min, float margin, int gallery_max_age, fvp_stream_t s);
 
 /* z-max of already materialised cubes [n][Z] -> [n] (n = B*J*X*Y): the first statement of
  * CenterNet.forward (cnns_2d.py:174) when it is called on its own. */

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 20          # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 21          # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -93,10 +93,13 @@ SIGNATURES = {
     "fvp_track_reid": [_P] * 17 + [_I] * 10 + [_F, _F, _I, _P],
     "fvp_zmax": [_P, _P, C.c_long, _I, _P],
     "fvp_person_boxes": [_P, _I, _P, _P, _P, _P, _P],
+    "fvp_plane_live_rows": [_P, _I, _I, _P, _P],
     "fvp_project_individual": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _G, _P, _P],
     "fvp_triplane_max": [_P, _P, _I, _I, _I, _P],
     "fvp_project_individual_triplane": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _G, _P, _I, _P, _P],
     "fvp_conv_stack_run": [C.POINTER(FvpConvOp), _I, _P, C.POINTER(_P), _I, _I, _P, _I, _P],
+    "fvp_conv_stack_reads_live_rows": [C.POINTER(FvpConvOp), _I, _I],
+    "fvp_conv_stack_run_rows": [C.POINTER(FvpConvOp), _I, _P, C.POINTER(_P), _I, _I, _P, _I, _P, _P],
     "fvp_conv_stack_run_fused_1d": [C.POINTER(FvpConvOp), _I, _P, _P, _P, _I, _P],
     "fvp_pack_conv": [_P, _P, _P, _P, _P, _P, _F, _I, C.POINTER(FvpConvOp), _P, _P],
     "fvp_nms_topk": [_P, _I, _I, _I, _I, _P, _P, _P, _P],

@@ -959,6 +959,7 @@ static const int kNoWino = int(env_size("FVP_CONV_NO_WINO", 0));          // 3x3
 static const int kNoPair = int(env_size("FVP_CONV_NO_PAIR", 0));          // no paired weight layouts (pixel-pair 7x7, paired transposed conv)
 static const int kNoK7 = int(env_size("FVP_CONV_NO_K7", 0));              // 7x7 convs on the pixel-pair form of k_conv_dma
 static const size_t kK7LdsPad = env_size("FVP_K7_LDS_KB", 0) * 1024;      // pad k_conv7's LDS request (fewer workgroups per CU)
+static const int kNoLiveRows = int(env_size("FVP_CONV_NO_LIVE_ROWS", 0)); // fvp_conv_stack_run_rows drops its live_rows (k_conv7 multiplies every row)
 static const int kNoPoolFuse = int(env_size("FVP_CONV_NO_POOL_FUSE", 0)); // the max-pool behind a Winograd conv as its own launch
 static const int kNoHeadFuse = int(env_size("FVP_CONV_NO_HEAD_FUSE", 0)); // the 1x1 conv behind a paired transposed conv as its own launch
 static const int kNoSkipFuse = int(env_size("FVP_CONV_NO_SKIP_FUSE", 0)); // a res-block's 1x1 skip conv as its own launch
@@ -1287,8 +1288,9 @@ static ConvArgs base_args(const FvpConvOp& op, const float* params, float* const
 
 static int plan_and_launch(const FvpConvOp& op, const float* params, float* const* bufs, int planes, const uint8_t* plane_valid,
                            int valid_div, hipStream_t s, float* pool_dst, const FvpConvOp* head, const FvpConvOp* skip = nullptr,
-                           bool plan_only = false) {
+                           bool plan_only = false, const int32_t* live_rows = nullptr) {
   ConvArgs a = base_args(op, params, bufs, planes, plane_valid, valid_div, pool_dst, head);
+  a.live_rows = live_rows;                             // (the stack's first op only; k_conv7 alone reads it)
   if (double(planes) * std::max(op.cin, op.cout) * a.OH * a.OW >= 2147483648.0) return FVP_ELIMIT;
   const ConvForm form = conv_form(op, planes, pool_dst != nullptr, head != nullptr);
   if (skip || plan_only) {                             // (eligibility: fused_skip())
@@ -1394,8 +1396,22 @@ using namespace fvp;
 
 extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* params, float* const* bufs, int nbufs,
                                   int planes, const uint8_t* plane_valid, int valid_div, fvp_stream_t s) {
+  return fvp_conv_stack_run_rows(ops, nops, params, bufs, nbufs, planes, plane_valid, valid_div, nullptr, s);
+}
+
+// 1 if a kernel of this stack reads the live_rows of fvp_conv_stack_run_rows (its first op takes k_conv7), else 0: the same
+// routing function the launch asks, so a caller computes the array only where it is read.
+extern "C" int fvp_conv_stack_reads_live_rows(const FvpConvOp* ops, int nops, int planes) {
+  if (!ops || nops <= 0 || planes <= 0 || kNoLiveRows || ops[0].kind != FVP_OP_CONV) return 0;
+  return conv_form(ops[0], planes, false, false) == ConvForm::K7 ? 1 : 0;   // (a 7x7 conv has no fused pool, head or skip)
+}
+
+extern "C" int fvp_conv_stack_run_rows(const FvpConvOp* ops, int nops, const float* params, float* const* bufs, int nbufs,
+                                       int planes, const uint8_t* plane_valid, int valid_div, const int32_t* live_rows,
+                                       fvp_stream_t s) {
   FVP_REQUIRE(ops && params && bufs && nops >= 0 && planes >= 0);
   if (planes == 0) return 0;
+  if (kNoLiveRows) live_rows = nullptr;
   // coarse profiling: one event pair around the whole stack (the max-pool launches inside are
   // counted in the time, not in the FLOPs)
   double flops = 0.0;
@@ -1434,7 +1450,7 @@ extern "C" int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* p
       const FvpConvOp* head = fused_head(ops, nops, i, nbufs, planes);
       const FvpConvOp* skip = (i < 64 && ((takes_skip >> i) & 1)) ? &ops[skip_of[i]] : nullptr;
       rc = plan_and_launch(op, params, bufs, planes, plane_valid, valid_div, as_stream(s),
-                           pool >= 0 ? bufs[ops[pool].dst] : nullptr, head, skip);
+                           pool >= 0 ? bufs[ops[pool].dst] : nullptr, head, skip, false, i == 0 ? live_rows : nullptr);
       if (!rc && head) ++i;
     } else {
       rc = FVP_EINVAL;

@@ -22,6 +22,14 @@
 // the pad behind each channel plane are out-of-range offsets: the DMA writes zeros.  The channel planes are CS words apart
 // with CS = 16 (mod 64): the four channel groups of an A read fall on four different bank quarters.
 // The order of the sum of an output - c, ky, kx ascending, four channels inside the MFMA - depends on nothing but the layer.
+//
+// Live rows (ConvArgs::live_rows, the stack's first op only): the caller promises that every channel of every input row of
+// plane p outside [r0, r1) is +0.0 (P2PNet's planes outside the person's box).  With the rows beyond the image (always
+// zero) that leaves one contiguous interval [lo, hi) of the tile's R + 6 input rows that can contribute.  A tile without
+// one issues no DMA, no weight load and no barrier and stores relu(bn(bias)); in a live tile a row outside the interval
+// issues neither its ds_reads nor its MFMAs (one scalar compare and branch per row: the row loop stays unrolled).  The bits
+// stay: the accumulators start at +0, a skipped MFMA would have added a sum of +-0 products, and under round-to-nearest an
+// accumulator never becomes -0, so acc + (+-0) = acc.
 #pragma once
 
 namespace fvp {
@@ -67,115 +75,144 @@ __global__ void __launch_bounds__(W / 16 * 64, (NCG == 4 && R <= 4) ? FVP_K7_OCC
   if (a.plane_valid && !a.plane_valid[plane / a.valid_div]) return;
   const int H = a.H, HW = H * W;
 
-  // epilogue vectors and the first channel group's weights: in flight under the tile DMA
+  // image rows that can hold a non-zero value: the plane's live range clamped to the image (wave-uniform: scalar loads)
+  int ylo = 0, yhi = H;
+  if (a.live_rows) {
+    const int r0 = __builtin_amdgcn_readfirstlane(a.live_rows[2 * plane]);
+    const int r1 = __builtin_amdgcn_readfirstlane(a.live_rows[2 * plane + 1]);
+    ylo = r0 < 0 ? 0 : r0 > H ? H : r0;
+    yhi = r1 < 0 ? 0 : r1 > H ? H : r1;
+  }
+  // ... and the tile's input rows [lo, hi) of 0 .. THp among them (row r = image row y0 - 3 + r)
+  const int lo = ylo > y0 - 3 ? ylo - (y0 - 3) : 0, hi = yhi < y0 + R + 3 ? yhi - (y0 - 3) : THp;
+  const unsigned nlive = hi > lo ? unsigned(hi - lo) : 0u;
+
+  // epilogue vectors: in flight under the tile DMA
   const int n = m;                                      // this lane's cout
   const float e_bias = a.epi[n], e_scale = a.epi[a.coutp + n], e_shift = a.epi[2 * a.coutp + n];
-  // 49 taps = 13 quads of 4 (the last one holds one tap): 13 global_load_dwordx4 per channel group instead of 49 dword
-  // loads - every vector instruction of a wave costs its SIMD ~12 cycles of matrix time
-  const float4* wl = reinterpret_cast<const float4*>(a.wts) + lane;
-  float4 bw[2][13];
-#pragma unroll
-  for (int tq = 0; tq < 13; ++tq) bw[0][tq] = wl[tq * 64];
-
-  // ---- input tile: [NCH][THp rows of (margin quad + W/4 quads)] + pad, one DMA round
-  if (!(FVP_K7_ABLATE & 1)) {
-    fvp_i32x4 rs;
-    const unsigned long long b = reinterpret_cast<unsigned long long>(a.src + size_t(plane) * a.cin * HW);
-    rs[0] = __builtin_amdgcn_readfirstlane(int(unsigned(b)));
-    rs[1] = __builtin_amdgcn_readfirstlane(int(unsigned(b >> 32) & 0xffffu));
-    rs[2] = a.cin * HW * 4;                             // channels >= cin fail the range check
-    rs[3] = 0x00020000;
-    const unsigned lds0 = FVP_LDS_BYTE_ADDRESS(smem);
-    // item j of this lane = item j - 1 + NT: (channel, row, quad) advance by compile-time steps with two carries instead of
-    // two divisions per item (the set-up in front of 784 MFMAs is matrix time too)
-    constexpr int kDCh = NT / QPC, kDRem = NT % QPC, kDRow = kDRem / QPR, kDQ = kDRem % QPR;
-    constexpr int kPadRow = QPC / QPR, kPadQ = QPC % QPR;       // a channel plane = kPadRow rows + kPadQ quads
-    const int it0 = wave * 64 + lane;
-    int ch = it0 / QPC, rem0 = it0 - ch * QPC;
-    int row = rem0 / QPR, q = rem0 - row * QPR;
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {
-      if ((wave + NW * j) * 64 + lane < NITEMS) {
-        const int y = y0 - 3 + row;
-        const bool ok = row < THp && q > 0 && y >= 0 && y < H;
-        const unsigned vo = ok ? unsigned((ch * H + y) * W + 4 * (q - 1)) * 4u : 0x80000000u;
-        asm_buffer_load_lds16(lds0 + unsigned(wave + NW * j) * 1024u, vo, rs, 0u);
-      }
-      ch += kDCh;
-      row += kDRow;
-      q += kDQ;
-      if (q >= QPR) {
-        q -= QPR;
-        ++row;
-      }
-      // past the end of the channel plane (row * QPR + q >= QPC): next channel
-      if (row > kPadRow || (row == kPadRow && q >= kPadQ)) {
-        ++ch;
-        row -= kPadRow;
-        q -= kPadQ;
-        if (q < 0) {
-          q += QPR;
-          --row;
-        }
-      }
-    }
-  }
-  wait_vmcnt(0);
-  __syncthreads();
 
   f32x4 acc[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-  const float* xs = smem + g * CS + wave * 16 + m + 1;  // channel g of a group, pixel x0 + m, tap kx = 0 (margin 4 - pad 3)
-  float av[2][7];
-  // One opaque word offset per three rows: the reads of those rows are `base + small constant` (ds_read2_b32 reaches 255
-  // words); left to itself hipcc rebuilds a base for almost every read pair (191 v_add_u32 per tile, 0.24 per MFMA).
-  int boff = 0;
-  auto fetch = [&](int set, int c, int r) {
-    if (r % 3 == 0) {
-      boff = c * 4 * CS + r * WP;
-      FVP_OPAQUE_V(boff);
-    }
-    const float* rowp = xs + boff + (r % 3) * WP;
+  if (nlive) {                                          // (a dead tile: nothing but the epilogue)
+    // the first channel group's weights, in flight under the tile DMA too
+    // 49 taps = 13 quads of 4 (the last one holds one tap): 13 global_load_dwordx4 per channel group instead of 49 dword
+    // loads - every vector instruction of a wave costs its SIMD ~12 cycles of matrix time
+    const float4* wl = reinterpret_cast<const float4*>(a.wts) + lane;
+    float4 bw[2][13];
 #pragma unroll
-    for (int kx = 0; kx < 7; ++kx) {
-      if (FVP_K7_ABLATE & 2) {
-        av[set][kx] = float(lane + kx);
-        FVP_OPAQUE_V(av[set][kx]);
-      } else {
-        av[set][kx] = rowp[kx];
-      }
-    }
-  };
-  fetch(0, 0, 0);
+    for (int tq = 0; tq < 13; ++tq) bw[0][tq] = wl[tq * 64];
+
+    // ---- input tile: [NCH][THp rows of (margin quad + W/4 quads)] + pad, one DMA round; rows outside the live range are
+    // out-of-range items like the rows outside the image (zeros without a fetch; the row loop does not read them)
+    if (!(FVP_K7_ABLATE & 1)) {
+      fvp_i32x4 rs;
+      const unsigned long long b = reinterpret_cast<unsigned long long>(a.src + size_t(plane) * a.cin * HW);
+      rs[0] = __builtin_amdgcn_readfirstlane(int(unsigned(b)));
+      rs[1] = __builtin_amdgcn_readfirstlane(int(unsigned(b >> 32) & 0xffffu));
+      rs[2] = a.cin * HW * 4;                             // channels >= cin fail the range check
+      rs[3] = 0x00020000;
+      const unsigned lds0 = FVP_LDS_BYTE_ADDRESS(smem);
+      // item j of this lane = item j - 1 + NT: (channel, row, quad) advance by compile-time steps with two carries instead of
+      // two divisions per item (the set-up in front of 784 MFMAs is matrix time too)
+      constexpr int kDCh = NT / QPC, kDRem = NT % QPC, kDRow = kDRem / QPR, kDQ = kDRem % QPR;
+      constexpr int kPadRow = QPC / QPR, kPadQ = QPC % QPR;       // a channel plane = kPadRow rows + kPadQ quads
+      const int it0 = wave * 64 + lane;
+      int ch = it0 / QPC, rem0 = it0 - ch * QPC;
+      int row = rem0 / QPR, q = rem0 - row * QPR;
 #pragma unroll
-  for (int c = 0; c < NCG; ++c) {
-    if (c + 1 < NCG && !(FVP_K7_ABLATE & 4)) {
-#pragma unroll
-      for (int tq = 0; tq < 13; ++tq) bw[(c + 1) & 1][tq] = wl[((c + 1) * 13 + tq) * 64];
-    }
-#pragma unroll
-    for (int r = 0; r < THp; ++r) {
-      const int cur = (c * THp + r) & 1, nxt = cur ^ 1;
-      __builtin_amdgcn_s_waitcnt(0xc07f);               // this row's activations (issued one step ago) have landed
-      __builtin_amdgcn_sched_barrier(0);
-      if (r + 1 < THp) fetch(nxt, c, r + 1);
-      else if (c + 1 < NCG) fetch(nxt, c + 1, 0);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int kx = 0; kx < 7; ++kx)
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          const int ky = r - j;
-          if (ky >= 0 && ky < 7) {
-            const int tp = ky * 7 + kx;
-            const float4& wq = bw[(FVP_K7_ABLATE & 4) ? 0 : (c & 1)][tp >> 2];
-            const float wv = (tp & 3) == 0 ? wq.x : (tp & 3) == 1 ? wq.y : (tp & 3) == 2 ? wq.z : wq.w;
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[cur][kx], wv, acc[j], 0, 0, 0);
+      for (int j = 0; j < NIT; ++j) {
+        if ((wave + NW * j) * 64 + lane < NITEMS) {
+          const int y = y0 - 3 + row;
+          const bool ok = row < THp && q > 0 && y >= ylo && y < yhi;
+          const unsigned vo = ok ? unsigned((ch * H + y) * W + 4 * (q - 1)) * 4u : 0x80000000u;
+          asm_buffer_load_lds16(lds0 + unsigned(wave + NW * j) * 1024u, vo, rs, 0u);
+        }
+        ch += kDCh;
+        row += kDRow;
+        q += kDQ;
+        if (q >= QPR) {
+          q -= QPR;
+          ++row;
+        }
+        // past the end of the channel plane (row * QPR + q >= QPC): next channel
+        if (row > kPadRow || (row == kPadRow && q >= kPadQ)) {
+          ++ch;
+          row -= kPadRow;
+          q -= kPadQ;
+          if (q < 0) {
+            q += QPR;
+            --row;
           }
         }
-      __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    wait_vmcnt(0);
+    __syncthreads();
+
+    const float* xs = smem + g * CS + wave * 16 + m + 1;  // channel g of a group, pixel x0 + m, tap kx = 0 (margin 4 - pad 3)
+    float av[2][7];
+    // One opaque word offset per three rows: the reads of those rows are `base + small constant` (ds_read2_b32 reaches 255
+    // words); left to itself hipcc rebuilds a base for almost every read pair (191 v_add_u32 per tile, 0.24 per MFMA).
+    int boff = 0;
+    // (`first`: the group's first live row may sit anywhere in its three rows and sets their base itself)
+    auto fetch = [&](int set, int c, int r, bool first = false) {
+      if (r % 3 == 0 || first) {
+        boff = c * 4 * CS + (r - r % 3) * WP;
+        FVP_OPAQUE_V(boff);
+      }
+      const float* rowp = xs + boff + (r % 3) * WP;
+#pragma unroll
+      for (int kx = 0; kx < 7; ++kx) {
+        if (FVP_K7_ABLATE & 2) {
+          av[set][kx] = float(lane + kx);
+          FVP_OPAQUE_V(av[set][kx]);
+        } else {
+          av[set][kx] = rowp[kx];
+        }
+      }
+    };
+    // Row r of a group waits for its operands in set r & 1 and fetches row r + 1 under its own MFMAs; the group's first live
+    // row has no live row in front of it and fetches for itself (once per group).  THp even: the set of a row does not depend
+    // on the group.
+    static_assert(THp % 2 == 0, "operand sets alternate by row");
+#pragma unroll
+    for (int c = 0; c < NCG; ++c) {
+      if (c + 1 < NCG && !(FVP_K7_ABLATE & 4)) {
+#pragma unroll
+        for (int tq = 0; tq < 13; ++tq) bw[(c + 1) & 1][tq] = wl[((c + 1) * 13 + tq) * 64];
+      }
+      // (the interval re-read per group: its row tests stay scalar compares at the point of use instead of lane masks that
+      // hipcc computes once and keeps in SGPR pairs across the groups)
+      int glo = lo;
+      unsigned gn = nlive;
+      FVP_OPAQUE_PAIR(glo, gn);
+#pragma unroll
+      for (int r = 0; r < THp; ++r) {
+        const int cur = r & 1, nxt = cur ^ 1;
+        const unsigned d = unsigned(r - glo);             // index of row r among the live rows
+        if (d < gn) {                                     // else a row of zeros: no ds_read, no MFMA
+          if (d == 0) fetch(cur, c, r, true);
+          __builtin_amdgcn_s_waitcnt(0xc07f);             // this row's activations (issued one step ago) have landed
+          __builtin_amdgcn_sched_barrier(0);
+          if (r + 1 < THp && d + 1 < gn) fetch(nxt, c, r + 1);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int kx = 0; kx < 7; ++kx)
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+              const int ky = r - j;
+              if (ky >= 0 && ky < 7) {
+                const int tp = ky * 7 + kx;
+                const float4& wq = bw[(FVP_K7_ABLATE & 4) ? 0 : (c & 1)][tp >> 2];
+                const float wv = (tp & 3) == 0 ? wq.x : (tp & 3) == 1 ? wq.y : (tp & 3) == 2 ? wq.z : wq.w;
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[cur][kx], wv, acc[j], 0, 0, 0);
+              }
+            }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
     }
   }
 

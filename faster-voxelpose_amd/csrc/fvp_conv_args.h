@@ -79,6 +79,10 @@ struct ConvArgs {
   const float* skip_epi;   // its bias | scale | shift, each coutp
   int skip_cin;            // its channels: 16 or 32 (4 or 8 MFMA steps: the kernels' template parameter SKIP)
   int skip_off;            // float offset of its LDS copy (BN vectors, then the weights) in dynamic LDS
+  // The stack's first op only (fvp_conv_stack_run_rows): [planes][2] = {r0, r1}, the caller's promise that every channel of
+  // every row of `src` outside [r0, r1) is +0.0 in that plane; nullptr: no promise.  k_conv7 skips those rows; every other
+  // kernel ignores the field.
+  const int32_t* live_rows;
 };
 
 

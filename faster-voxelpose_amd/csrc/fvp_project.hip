@@ -1293,6 +1293,27 @@ k_person_boxes(const float* __restrict__ centers, int n, const float* __restrict
   }
 }
 
+// fvp_plane_live_rows: the rows of a person's three planes that the projection can write (rows of the x-y and x-z planes
+// are x, rows of the y-z plane are y), cube-relative: {start - tl, end - tl} clamped to [0, C]; an empty window in any axis
+// leaves all three planes at the caller's zero fill: {0, 0}.
+__global__ void __launch_bounds__(64)
+k_plane_live_rows(const int* __restrict__ boxes, int n, int C, int* __restrict__ live_rows) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const int* b = boxes + size_t(i) * 9;
+  const bool empty = b[3] >= b[6] || b[4] >= b[7] || b[5] >= b[8];
+  int lo[2], hi[2];
+  for (int a = 0; a < 2; ++a) {
+    const int r0 = b[3 + a] - b[a], r1 = b[6 + a] - b[a];
+    lo[a] = empty || r0 < 0 ? 0 : r0 > C ? C : r0;
+    hi[a] = empty || r1 < 0 ? 0 : r1 > C ? C : r1;
+  }
+  int* o = live_rows + size_t(i) * 6;
+  o[0] = lo[0]; o[1] = hi[0];
+  o[2] = lo[0]; o[3] = hi[0];
+  o[4] = lo[1]; o[5] = hi[1];
+}
+
 }  // namespace fvp
 
 // =============================================================================================
@@ -1525,6 +1546,13 @@ extern "C" int fvp_person_boxes(const float* centers, int n, const float* consts
   hipLaunchKernelGGL(k_person_boxes, dim3(ceil_div(n, 64)), dim3(64), 0, as_stream(s), centers, n, consts,
                      fine_cube[0], fine_cube[1], fine_cube[2], fine_cube[3], fine_cube[4], fine_cube[5], boxes,
                      offset);
+  return launch_status();
+}
+
+extern "C" int fvp_plane_live_rows(const int32_t* boxes, int nP, int C, int32_t* live_rows, fvp_stream_t s) {
+  FVP_REQUIRE(boxes && live_rows && nP >= 0 && C > 0);
+  if (nP == 0) return 0;
+  hipLaunchKernelGGL(k_plane_live_rows, dim3(ceil_div(nP, 64)), dim3(64), 0, as_stream(s), boxes, nP, C, live_rows);
   return launch_status();
 }
 

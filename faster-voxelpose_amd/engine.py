@@ -135,6 +135,10 @@ class HotPath:
         # by default they are projected directly (fvp_project_columns, same bits) and the [B,J,X,Y,Z] cubes are never
         # written.  True: materialise them (kept in self.last["cubes"]; the drop-in ProjectLayer always materialises).
         self.keep_hdn_cubes = False
+        # P2PNet's 7x7 front conv is told which rows of each plane the projection can have written (fvp_plane_live_rows ->
+        # fvp_conv_stack_run_rows: the rows outside a person's box stay at the zero fill and are not multiplied; same bits).
+        # False: no promise is passed (the A/B switch).
+        self.conv_live_rows = True
 
     # ---------------------------------------------------------------------------------------------
     def stream(self):
@@ -321,9 +325,10 @@ class HotPath:
                    self.F, self.Hd, _ptr(self.wn_params), self.stream())
 
     # ---- conv stack ----------------------------------------------------------------------------------------
-    def run_stack(self, name, x, planes, plane_valid=None, valid_div=1, fresh=()):
+    def run_stack(self, name, x, planes, plane_valid=None, valid_div=1, fresh=(), live_rows=None):
         """`fresh`: output names whose buffer is a new tensor instead of the stack's reused scratch - the caller may hand it
-        out (HDN's public heatmaps) without a copy launch."""
+        out (HDN's public heatmaps) without a copy launch.  `live_rows`: int32 [planes, 2], the promise of
+        fvp_conv_stack_run_rows about `x` (rows outside [r0, r1) of a plane are +0.0)."""
         spec = self.specs[name]
         bufs = [x]
         own = {spec.outputs[k] for k in fresh}
@@ -331,8 +336,8 @@ class HotPath:
             bufs.append(torch.empty((planes, c, h, w), device=self.device) if i in own
                         else self.scratch(f"{name}.buf{i}", (planes, c, h, w)))
         arr = (C.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
-        self._call("fvp_conv_stack_run", spec.op_array, len(spec.ops), _ptr(self.params[name]), arr, len(bufs),
-                   planes, _ptr(plane_valid), valid_div, self.stream())
+        self._call("fvp_conv_stack_run_rows", spec.op_array, len(spec.ops), _ptr(self.params[name]), arr, len(bufs),
+                   planes, _ptr(plane_valid), valid_div, _ptr(live_rows), self.stream())
         return {k: bufs[i] for k, i in spec.outputs.items()}
 
     def run_stack_fused_1d(self, name, x, planes, fresh=False):
@@ -436,6 +441,14 @@ class HotPath:
                    _ptr(offset), self.stream())
         return boxes, offset
 
+    def plane_live_rows(self, boxes):
+        """[n*3, 2] int32: the rows of each person's three planes inside the box (fvp_plane_live_rows); a scratch buffer
+        with a stable address, like `boxes`."""
+        n = boxes.shape[0]
+        rows = self.scratch("live_rows", (n * 3, 2), torch.int32)
+        self._call("fvp_plane_live_rows", _ptr(boxes), n, self.C, _ptr(rows), self.stream())
+        return rows
+
     def softargmax_weightnet(self, joint_features, grids=None):
         """Standalone launch of the fused soft-argmax + WeightNet kernel on features in the
         reference's layout [3, P, J, C, C] (joint_localization_net.py:20-34, weight_net.py:69-80).
@@ -485,6 +498,10 @@ class HotPath:
         pf = self.person_frame(B, N)
         centers2d = proposal_centers.view(nP, 7)
         boxes, offset = self.person_boxes(centers2d)
+        # (computed only where a kernel reads it: a cube whose front conv does not take k_conv7 has no use for the launch)
+        spec = self.specs["conv_net"]
+        reads = self.conv_live_rows and self.lib.fvp_conv_stack_reads_live_rows(spec.op_array, len(spec.ops), nP * 3) == 1
+        live_rows = self.plane_live_rows(boxes) if reads else None
         fa = self.fine_axes
         planes = self.scratch("planes", (nP, 3, J, Cn, Cn), zero=True)
         if fused:
@@ -498,7 +515,8 @@ class HotPath:
                        _ptr(boxes), _ptr(fa[0]), _ptr(fa[1]), _ptr(fa[2]), _ptr(self.fine_dev), Cn, nP, C.byref(g),
                        _ptr(cubes), s)
             self._call("fvp_triplane_max", _ptr(cubes), _ptr(planes), nP, J, Cn, s)
-        feat = self.run_stack("conv_net", planes.view(nP * 3, J, Cn, Cn), nP * 3, valid, 3)["out"]
+        # both projection paths leave the rows outside the box at the zero fill (fused) or write +0.0 there (materialised)
+        feat = self.run_stack("conv_net", planes.view(nP * 3, J, Cn, Cn), nP * 3, valid, 3, live_rows=live_rows)["out"]
         pose2d = self.scratch("pose2d", (nP, 3, J, 2))
         pmax = self.scratch("pmax", (nP, 3, J))
         wgt = self.scratch("wgt", (nP, 3, J))

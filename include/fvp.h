@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 20
+#define FVP_ABI_VERSION 21
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -346,6 +346,14 @@ int fvp_zmax(const float* cubes, float* zmax, long n, int Z, fvp_stream_t s);
 int fvp_person_boxes(const float* centers, int n, const float* consts, const int32_t* fine_cube,
                      int32_t* boxes, float* offset, fvp_stream_t s);
 
+/* The rows of each person's three orthographic planes that the individual projection can write (ABI 21).  The cube is
+ * masked by the box (project_individual.py:113-121): outside [start, end) every voxel stays zero, so in the x-y and x-z
+ * planes (rows = x) the rows outside [start0 - tl0, end0 - tl0) and in the y-z plane (rows = y) the rows outside
+ * [start1 - tl1, end1 - tl1) are +0.0 in every channel.  boxes = [nP][9] of fvp_person_boxes; live_rows = [nP*3][2]
+ * int32 = {r0, r1} per plane, clamped to [0, C]; an empty window in any axis gives {0, 0} for all three planes.
+ * The array is what fvp_conv_stack_run_rows takes for P2PNet's input.  One launch, no host synchronisation. */
+int fvp_plane_live_rows(const int32_t* boxes, int nP, int C, int32_t* live_rows, fvp_stream_t s);
+
 /* ---- a-14 sampling part (drop-in, materialises the cube) ---------------------------------
  * cubes[p][j][C][C][C]; person p lives in frame person_frame[p]; fine-grid axis tables
  * fx/fy/fz of lengths fine[0..2].  Windows outside [start,end) stay 0; persons with
@@ -424,6 +432,21 @@ typedef struct FvpConvOp {
  * plane_valid (may be NULL): planes with plane_valid[n / valid_div] == 0 are skipped. */
 int fvp_conv_stack_run(const FvpConvOp* ops, int nops, const float* params, float* const* bufs, int nbufs,
                        int planes, const uint8_t* plane_valid, int valid_div, fvp_stream_t s);
+
+/* fvp_conv_stack_run with a promise about the stack's input (ABI 21; P2PNet on the masked tri-planes,
+ * joint_localization_net.py:75-80 on the cubes of project_individual.py:113-121).  live_rows (device memory, may be
+ * NULL: then this IS fvp_conv_stack_run) = [planes][2] int32 = {r0, r1}: the caller promises that in plane p of
+ * bufs[ops[0].src] every channel of every row outside [r0, r1) is +0.0.  The range is clamped to [0, H]; r0 >= r1 says
+ * the whole plane is zero.  The 7x7 front conv (k_conv7) then multiplies no row of zeros and fetches none; every other
+ * kernel, and every op but ops[0], ignores the array.  The result has the same bits as without the array.  A promise
+ * that does not hold gives a wrong result (the rows are treated as zero), never an out-of-bounds access.
+ * fvp_conv_stack_reads_live_rows (host only, no launch): 1 if some kernel of the stack would read the array at this plane
+ * count - ops[0] takes k_conv7 (7x7, cout <= 16, maps 64 or 128 wide, cin <= 20) -, else 0: a caller need not compute an
+ * array that nothing reads (a miniature cube, CenterNet's stack). */
+int fvp_conv_stack_reads_live_rows(const FvpConvOp* ops, int nops, int planes);
+int fvp_conv_stack_run_rows(const FvpConvOp* ops, int nops, const float* params, float* const* bufs, int nbufs,
+                            int planes, const uint8_t* plane_valid, int valid_div, const int32_t* live_rows,
+                            fvp_stream_t s);
 
 /* The same interpreter for a 1-D stack (H = 1, W <= 24, cout <= 128: C2CNet) fused into ONE
  * kernel, one workgroup per plane, activations resident in LDS.  in = [planes][cin][W] (buffer

@@ -537,9 +537,10 @@ __device__ __forceinline__ void conv_epilogue_wide(KArgsPtr a, const float* epi,
 // KS (split K; small maps with long reductions: CenterNet's 3x3 layers on the 20x20 / 40x40 levels, 64-128
 // channels): with a handful of planes such a layer has fewer pixel blocks than the chip has SIMDs, and a wave's
 // output is ONE dependent chain of cinp*9/2 = 288-576 MFMAs (64 cycles each: 8-15 us before the first store).
-// Here the four waves of a workgroup share one pixel block and each takes every fourth channel pair of a chunk;
-// the four partial tiles are added in the fixed order ((w0 + w1) + w2) + w3 through LDS and wave 0 runs the
-// epilogue.  Chosen from the layer SHAPE only, so a frame's result does not depend on its batch.
+// Here the four waves of a workgroup share its PB pixel blocks (whole image rows: 32 * PB pixels) and each takes every
+// fourth channel pair of a chunk; the four partial tiles are added in the fixed order ((w0 + w1) + w2) + w3 through
+// LDS and wave 0 runs the epilogue.  The form is chosen from the layer SHAPE only and PB does not change a pixel's chain
+// (ksplit_blocks()), so a frame's result does not depend on its batch.
 template <int KH, int KW, int CB, int PB, bool PAIR = false, bool TPAIR = false, bool KS = false>
 __global__ void __launch_bounds__(256, (KH * KW == 1 && !(TPAIR && CB * PB == 4 && CB == 2)) ? FVP_CONV_1X1_OCC : 2) k_conv_dma(ConvArgs a) {
   HIP_DYNAMIC_SHARED(float, smem)
@@ -966,6 +967,9 @@ static const int kNoSkipFuse = int(env_size("FVP_CONV_NO_SKIP_FUSE", 0)); // a r
 static const int kNoReg = int(env_size("FVP_CONV_NO_REG", 0));            // 1x1 / transposed convs on k_conv_dma
 static const int kRegWgs = int(env_size("FVP_CONV_REG_WGS", 0));          // k_conv_reg: workgroups per CU
 static const int kNoKSplit = int(env_size("FVP_CONV_NO_KSPLIT", 0));      // no split-K form for the small-map 3x3 layers
+// FVP_CONV_KS_PB: force the pixel blocks per workgroup (1 / 2 / 4) of the split-K form (read per call in the diagnostics
+// build, like FVP_CONV_REG_MIN_TILES below: a test runs the same stack through every tiling; a constant in the product)
+static int force_ks_pb() { return int(env_size("FVP_CONV_KS_PB", 0)); }
 // FVP_CONV_REG_MIN_TILES: least number of 32-pixel tiles at which k_conv_reg takes an op
 // (read per call in the diagnostics build, so that a test can run the same stack through both kernels; a constant in the product)
 // Transposed convs gain from 200 tiles on (B = 1: 128 -> 64 22.6 -> 18.6 us at 240 tiles, 64 -> 32 17.2 -> 12.5 us at 960; CenterNet at
@@ -1093,7 +1097,7 @@ ConvForm conv_form(const FvpConvOp& op, int planes, bool has_pool_dst, bool has_
   // 128->128 @20x20 32.3 -> 18.7 us at one plane (33.3 -> 31.0 at eight); the 40x40 level gains nothing at one plane
   // (18.9 -> 18.2 us) and doubles at eight planes (every workgroup stages the same weight slice), so it stays on the
   // plain form.  A SHAPE rule (map size, channels), never the number of planes: a frame's result does not depend on
-  // the batch it is computed in.
+  // the batch it is computed in.  (How many image rows a workgroup takes does depend on the planes: ksplit_blocks().)
   if (!kNoKSplit && kh == 3 && kw == 3 && op.w % 4 == 0 && op.w <= 32 && op.h * op.w >= 256 && op.h * op.w <= 576 &&
       op.cinp >= 64 && op.cinp % 8 == 0 && !kNoDma)
     return ConvForm::KSplit;
@@ -1214,8 +1218,29 @@ static int launch_k7_form(const FvpConvOp& op, ConvArgs a, const float* params, 
   return op.w == 64 ? launch_k7<64, 5>(a, grid, s) : launch_k7<128, 5>(a, grid, s);
 }
 
+// Pixel blocks per workgroup of the split-K form.  One block is one image row of a 20-wide map (20 of 32 lanes), and every
+// workgroup streams the whole weight slice of its 32 couts through LDS, eight chunk round trips long: with many planes
+// the launch is several rounds of such workgroups.  Two / four blocks are 3 / 6 rows of such a map (60 / 120 of 64 / 128
+// lanes) behind ONE copy of the slice: a third / a sixth of the workgroups, 30 % fewer MFMAs.  Measured at 128 -> 128 @20x20
+// (DESIGN 4.2): 8 planes 27.4 -> 24.3 us with two blocks (39.5 with four), 32 planes 95.2 -> 61.5 with four (69.0 with two),
+// <= 6 planes one block is 2 us faster than two.  A
+// pixel's chain is the same in every tiling (wave w takes the channel pairs 2w, 2w + 8, ... in order, the taps in (ky, kx)
+// order, the partials are added ((w0 + w1) + w2) + w3), so the bits do not depend on the choice and it may depend on the
+// amount of work, as reg_takes() does: one block while the launch at one row per workgroup (rows x planes x cout blocks)
+// fits the chip at once, above that the fewest blocks whose grid does.  "Fits": kKsFit workgroups, two on each of the 256
+// CUs of the MI355X - a constant, so that every device (and the CPU emulation, a 3-CU device) plans what the product plans.
+constexpr long kKsFit = 512;
+static int ksplit_blocks(const FvpConvOp& op, int planes) {
+  const int forced = force_ks_pb();
+  if (forced == 1 || forced == 2 || forced == 4) return forced;
+  const long per_tile = long(planes) * (op.coutp / 32);
+  if (op.h * per_tile <= kKsFit) return 1;
+  return ceil_div(op.h, std::max(1, 64 / op.w)) * per_tile <= kKsFit ? 2 : 4;   // (64 / w: rows of a two-block tile)
+}
+
 // The direct forms of k_conv / k_conv_dma.  Direct: all couts per workgroup (CB = coutp/32), the tile shaped to cover full
-// image rows where possible.  KSplit: one image row (plus masked lanes) per workgroup.  Pair7: tile columns are pixel pairs.
+// image rows where possible.  KSplit: 32 * ksplit_blocks() pixels in whole image rows (plus masked lanes) per workgroup.
+// Pair7: tile columns are pixel pairs.
 static int launch_direct_form(const FvpConvOp& op, ConvArgs a, const float* params, int planes, hipStream_t s, ConvForm form) {
   const bool tr = op.kind == FVP_OP_CONVT2, pair = form == ConvForm::Pair7, ksplit = form == ConvForm::KSplit;
   const int kh = tr ? 1 : op.kh, kw = tr ? 1 : op.kw;
@@ -1230,13 +1255,20 @@ static int launch_direct_form(const FvpConvOp& op, ConvArgs a, const float* para
     while (PB > 1 && (px_total + 128 * PB - 1) / (128 * PB) * CBfull < 512) PB >>= 1;
   }
   if (kForcePB && CB * kForcePB <= 4) PB = kForcePB;
-  if (ksplit) CB = PB = 1;
+  if (ksplit) {
+    CB = 1;
+    PB = ksplit_blocks(op, planes);
+  }
   dim3 grid;
   size_t lds;
   if (int e = plan_tiles(op, params, planes, form, CB, PB, a, &grid, &lds)) return e;
   ProfScope ps(FVP_K_CONV, s, conv_flops(op, planes), 1, prof_level() >= 2);
   if (ksplit) {
-    hipLaunchKernelGGL((k_conv_dma<3, 3, 1, 1, false, false, true>), grid, dim3(256), lds, s, a);
+    switch (PB) {
+      case 1: hipLaunchKernelGGL((k_conv_dma<3, 3, 1, 1, false, false, true>), grid, dim3(256), lds, s, a); break;
+      case 2: hipLaunchKernelGGL((k_conv_dma<3, 3, 1, 2, false, false, true>), grid, dim3(256), lds, s, a); break;
+      default: hipLaunchKernelGGL((k_conv_dma<3, 3, 1, 4, false, false, true>), grid, dim3(256), lds, s, a); break;
+    }
     return launch_status();
   }
   if (!pair) return dispatch_conv(kh, kw, CB, PB, a, grid, lds, s);

@@ -1,5 +1,5 @@
-"""What every stream-side wrapper (tracker, smoother, overlay, crops, visibility, triangulation, re-fit, ingest) does before
-it launches: the library seam, the "GPU only" refusal, the tensor checks, pointers and the stream handle for the C ABI, and
+"""What every stream-side wrapper (tracker, smoother, limb model, overlay, crops, visibility, triangulation, re-fit, ingest) does
+before it launches: the library seam, the "GPU only" refusal, the tensor checks, pointers and the stream handle for the C ABI, and
 the upload-once tables that turn sequence names and camera dicts into device tensors.  No arithmetic on tensors happens here
 and nothing synchronises with the host."""
 import ctypes as C

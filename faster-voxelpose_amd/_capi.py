@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 21          # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 22          # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -22,6 +22,8 @@ FVP_SIG_BINS = 64
 FVP_SIG_MAX_SAMPLES = 16384
 FVP_REID_MAX_GALLERY = 64
 FVP_REID_MAX_WINDOW = 1024
+FVP_LIMB_MAX = 64
+FVP_LIMB_LEARNED, FVP_LIMB_LEARNING, FVP_LIMB_NOT_MEASURED, FVP_LIMB_OUTLIER, FVP_LIMB_RELEARNED, FVP_LIMB_INVALID = 1, 2, 0, -1, -2, -3
 FVP_VIS_MAX_PEOPLE = 32
 FVP_VIS_MAX_PRIMS = 64
 FVP_TRI_MAX_RADIUS = 8
@@ -88,6 +90,8 @@ SIGNATURES = {
     "fvp_joint_evidence": [_P, _P, _P, _P, _I, _I, _G, _P, _P, _P],
     "fvp_track_update": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "fvp_track_smooth": [_P] * 12 + [_I] * 5 + [_F] * 6 + [_I, _P],
+    "fvp_limb_learn": [_P] * 5 + [C.POINTER(C.c_int32), _I] + [_P] * 8 + [_I] * 5 + [_F, _I, _I, _F, _F, _I, _P],
+    "fvp_limb_fit": [_P] * 4 + [C.POINTER(C.c_int32), _I, _P, _P, _I, _I, _I, _F, _F, _I, _P],
     "fvp_person_signature": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _I,
                              _I, _F, _P, _P, _P],
     "fvp_track_reid": [_P] * 17 + [_I] * 10 + [_F, _F, _I, _P],

@@ -514,6 +514,237 @@ k_track_smooth(const float* __restrict__ poses, const int* __restrict__ frame_se
   }
 }
 
+// ---- limb model (ABI 22): bone lengths per track, and poses constrained to them ---------------------------------------------
+// The definitions are in include/fvp.h.  k_limb_learn is k_track_smooth's shape with a limb where that has a joint: a thread
+// owns one (s, t, l), keeps len, var, cnt, out and the slot's id in registers and walks the B frames in order - one launch per
+// batch, state read once at entry and written once at exit.  Every thread of a slot recomputes the id transition; the l == 0
+// thread stores limb_id.  The state is rewritten in place, so the same hazard applies: a workgroup is one wave that holds
+// 64 / L WHOLE slots (56 of 64 lanes at L = 14, 57 at L = 19, one slot from L = 33 on), its loads precede its stores in
+// program order, and no other wave touches the slot; the wave barrier behind the entry loads emits no instruction and is the
+// hand-over point of the CPU emulation.  The limb table travels in the kernel's parameter block (uint8 pairs), as in the draw
+// kernels.  Each element of the outputs has one writer: the thread of the track slot a valid detection sits in, or thread
+// t == n for an invalid one (T >= N).  No LDS, no atomics, no workgroup barrier.  Latency-bound: nothing is tuned.
+constexpr int kLimbThreads = 64;
+static_assert(FVP_LIMB_MAX <= kLimbThreads, "a wave holds at least one whole slot");
+static_assert(FVP_MAX_JOINTS <= 32, "k_limb_fit keeps the support mask in one register");
+
+struct LimbPrm {
+  uint8_t limb[FVP_LIMB_MAX][2];
+};
+
+__device__ __forceinline__ bool limb_finite(float x0, float x1, float x2) {
+  return fabsf(x0) <= FLT_MAX && fabsf(x1) <= FLT_MAX && fabsf(x2) <= FLT_MAX;                     // false for NaN, Inf
+}
+
+__device__ __forceinline__ float limb_norm(float d0, float d1, float d2) {
+  return sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+}
+
+__global__ void __launch_bounds__(kLimbThreads)
+k_limb_learn(const float* __restrict__ poses, const int* __restrict__ frame_set, const int* __restrict__ ids,
+             const int* __restrict__ slots, const float* __restrict__ conf, const LimbPrm prm, int L,
+             float* __restrict__ limb_len, float* __restrict__ limb_var, int* __restrict__ limb_cnt,
+             int* __restrict__ limb_out, int* __restrict__ limb_id, float* __restrict__ target,
+             float* __restrict__ limb_obs, int* __restrict__ limb_state, int B, int N, int J, int nseq, int T,
+             float conf_min, int min_frames, int window, float gate_sigma, float gate_mm, int relearn) {
+  const int s = blockIdx.y, spb = kLimbThreads / L, tl = int(threadIdx.x) / L;
+  const int t = blockIdx.x * spb + tl, l = int(threadIdx.x) - tl * L;
+  const bool active = tl < spb && t < T;
+  const size_t st = size_t(s) * T + t, sl = st * L + l;
+  float len = 0.0f, var = 0.0f;
+  int cnt = 0, nout = 0, id = -1;
+  if (active) {
+    len = limb_len[sl];
+    var = limb_var[sl];
+    cnt = limb_cnt[sl];
+    nout = limb_out[sl];
+    id = limb_id[st];
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (!active) return;
+  const int ji = prm.limb[l][0], jk = prm.limb[l][1];
+
+#pragma unroll 1
+  for (int b = 0; b < B; ++b) {
+    const int fs = frame_set ? frame_set[b] : 0;
+    if (fs != s) {
+      // a frame of no sequence: nobody owns it, the workgroups of sequence 0 write it as invalid
+      if (s == 0 && (fs < 0 || fs >= nseq) && t < N) {
+        const size_t o = (size_t(b) * N + t) * L + l;
+        target[o] = 0.0f;
+        limb_obs[2 * o] = -1.0f;
+        limb_obs[2 * o + 1] = 0.0f;
+        limb_state[o] = FVP_LIMB_INVALID;
+      }
+      continue;
+    }
+    // the detections of this frame that sit in track slot t (a bit per n; the lowest one is measured), and whether
+    // detection slot n == t is an invalid one, which this thread writes as such
+    unsigned mine = 0;
+    int first = -1;
+    bool inval = false;
+#pragma unroll 1
+    for (int n = 0; n < N; ++n) {
+      const int i = ids[size_t(b) * N + n], sn = slots[size_t(b) * N + n];
+      const bool ok = i >= 0 && sn >= 0 && sn < T;
+      if (ok && sn == t) {
+        mine |= 1u << n;
+        if (first < 0) first = n;
+      }
+      if (!ok && n == t) inval = true;
+    }
+    if (inval) {
+      const size_t o = (size_t(b) * N + t) * L + l;
+      target[o] = 0.0f;
+      limb_obs[2 * o] = -1.0f;
+      limb_obs[2 * o + 1] = 0.0f;
+      limb_state[o] = FVP_LIMB_INVALID;
+    }
+    if (first < 0) continue;                                   // the lengths survive coasting
+    const size_t row = (size_t(b) * N + first) * J;
+    const int nid = ids[size_t(b) * N + first];
+    if (id != nid) {                                           // a birth, a reuse or an eviction: every limb starts over
+      id = nid;
+      len = var = 0.0f;
+      cnt = nout = 0;
+    }
+    const float* pi = poses + (row + ji) * 5;
+    const float* pk = poses + (row + jk) * 5;
+    const float a0 = pi[0], a1 = pi[1], a2 = pi[2], c0 = pk[0], c1 = pk[1], c2 = pk[2];
+    bool measured = limb_finite(a0, a1, a2) && limb_finite(c0, c1, c2);
+    if (measured && conf) measured = conf[row + ji] >= conf_min && conf[row + jk] >= conf_min;
+    float d = -1.0f, e = 0.0f;
+    int state = FVP_LIMB_NOT_MEASURED;
+    if (measured) {
+      const float dd = limb_norm(__fsub_rn(c0, a0), __fsub_rn(c1, a1), __fsub_rn(c2, a2));
+      if (dd > 0.0f && dd <= FLT_MAX) {
+        d = dd;
+        e = __fsub_rn(d, len);
+        bool pass = true;
+        if (cnt >= min_frames) pass = fabsf(e) <= fmaxf(__fmul_rn(gate_sigma, sqrtf(var)), gate_mm);
+        if (pass) {
+          nout = 0;
+          cnt = cnt + 1 < window ? cnt + 1 : window;
+          const float g = __fdiv_rn(1.0f, float(cnt));
+          len = __fadd_rn(len, __fmul_rn(g, e));
+          var = __fadd_rn(var, __fmul_rn(g, __fsub_rn(__fmul_rn(e, __fsub_rn(d, len)), var)));
+          state = cnt >= min_frames ? FVP_LIMB_LEARNED : FVP_LIMB_LEARNING;
+        } else if (++nout > relearn) {
+          len = d;
+          var = 0.0f;
+          cnt = 1;
+          nout = 0;
+          state = FVP_LIMB_RELEARNED;
+        } else {
+          state = FVP_LIMB_OUTLIER;
+        }
+      }
+    }
+    const float tg = cnt >= min_frames ? len : 0.0f;
+#pragma unroll 1
+    for (int n = first; n < N; ++n) {
+      if (!(mine >> n & 1u)) continue;
+      const size_t o = (size_t(b) * N + n) * L + l;
+      target[o] = tg;
+      limb_obs[2 * o] = d;
+      limb_obs[2 * o + 1] = e;
+      limb_state[o] = state;
+    }
+  }
+
+  limb_len[sl] = len;
+  limb_var[sl] = var;
+  limb_cnt[sl] = cnt;
+  limb_out[sl] = nout;
+  if (l == 0) limb_id[st] = id;
+}
+
+// k_limb_fit: one lane per person (b, n), 64 people per workgroup (one wave).  The sweeps index joints dynamically, which in a
+// register array would become scratch, so the workgroup stages its poses in LDS as [J * 3][64], lane-minor: a lane's LDS
+// access always hits bank = lane, conflict-free on the 64 x 4 B banks; 24 KB at J = 32.  The [J][5] rows of the 64 people are
+// one contiguous piece of memory: loaded coalesced by the whole workgroup and transposed on the way in, written back the same
+// way (columns 3:5 straight from the input), so fitted may be poses itself - a workgroup has read all of its rows before it
+// writes one and no other workgroup touches them.  The support mask is one register per lane; the limb pair of step l is
+// uniform over the wave, a scalar load from the parameter block; target is read from global memory in every sweep (a load
+// whose address does not depend on the chain).  Latency-bound: iters * L dependent steps per lane of one sqrt, one divide
+// and a dozen LDS accesses each; nothing beyond the one launch is tuned.
+__global__ void __launch_bounds__(kLimbThreads)
+k_limb_fit(const float* poses, const int* __restrict__ ids, const float* __restrict__ conf,
+           const float* __restrict__ target, const LimbPrm prm, int L, float* fitted, float* __restrict__ resid, int BN, int J,
+           float conf_min, float stiffness, int iters) {
+  __shared__ float s_y[FVP_MAX_JOINTS * 3 * kLimbThreads];
+  const int lane = threadIdx.x, base = blockIdx.x * kLimbThreads, row = J * 5;
+  const int np = BN - base < kLimbThreads ? BN - base : kLimbThreads, total = np * row;
+  const size_t g0 = size_t(base) * row;
+#pragma unroll 1
+  for (int i = lane; i < total; i += kLimbThreads) {
+    const int p = i / row, r = i - p * row, j = r / 5, c = r - j * 5;
+    if (c < 3) s_y[(j * 3 + c) * kLimbThreads + p] = poses[g0 + i];
+  }
+  __syncthreads();
+
+  const size_t me = size_t(base) + lane;
+  float* y = s_y + lane;
+  bool valid = false;
+  if (lane < np) valid = poses[me * row + 3] >= 0.0f && (!ids || ids[me] >= 0);
+  if (valid) {
+    unsigned m = 0;                                            // bit j: joint j of the input pose is supported
+#pragma unroll 1
+    for (int j = 0; j < J; ++j) {
+      bool ok = limb_finite(y[(j * 3) * kLimbThreads], y[(j * 3 + 1) * kLimbThreads], y[(j * 3 + 2) * kLimbThreads]);
+      if (ok && conf) ok = conf[me * J + j] >= conf_min;
+      m |= unsigned(ok) << j;
+    }
+#pragma unroll 1
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll 1
+      for (int l = 0; l < L; ++l) {
+        const float tg = target[me * L + l];
+        if (!(tg > 0.0f)) continue;                            // unconstrained: 0, negative, NaN
+        const int i = prm.limb[l][0], k = prm.limb[l][1];
+        float* yi = y + i * 3 * kLimbThreads;
+        float* yk = y + k * 3 * kLimbThreads;
+        const float i0 = yi[0], i1 = yi[kLimbThreads], i2 = yi[2 * kLimbThreads];
+        const float k0 = yk[0], k1 = yk[kLimbThreads], k2 = yk[2 * kLimbThreads];
+        const float d0 = __fsub_rn(k0, i0), d1 = __fsub_rn(k1, i1), d2 = __fsub_rn(k2, i2);
+        const float d = limb_norm(d0, d1, d2);
+        if (!(d > 0.0f && d <= FLT_MAX)) continue;
+        const float sc = __fdiv_rn(__fmul_rn(stiffness, __fsub_rn(d, tg)), d);
+        const bool mi = m >> i & 1u, mk = m >> k & 1u;
+        const float wi = mi == mk ? 0.5f : (mi ? 0.0f : 1.0f), wk = mi == mk ? 0.5f : (mi ? 1.0f : 0.0f);
+        const float si = __fmul_rn(wi, sc), sk = __fmul_rn(wk, sc);
+        yi[0] = __fadd_rn(i0, __fmul_rn(si, d0));
+        yi[kLimbThreads] = __fadd_rn(i1, __fmul_rn(si, d1));
+        yi[2 * kLimbThreads] = __fadd_rn(i2, __fmul_rn(si, d2));
+        yk[0] = __fsub_rn(k0, __fmul_rn(sk, d0));
+        yk[kLimbThreads] = __fsub_rn(k1, __fmul_rn(sk, d1));
+        yk[2 * kLimbThreads] = __fsub_rn(k2, __fmul_rn(sk, d2));
+      }
+    }
+  }
+  if (resid && lane < np) {
+#pragma unroll 1
+    for (int l = 0; l < L; ++l) {
+      float r = 0.0f;
+      const float tg = target[me * L + l];
+      if (valid && tg > 0.0f) {
+        const float* yi = y + prm.limb[l][0] * 3 * kLimbThreads;
+        const float* yk = y + prm.limb[l][1] * 3 * kLimbThreads;
+        const float d = limb_norm(__fsub_rn(yk[0], yi[0]), __fsub_rn(yk[kLimbThreads], yi[kLimbThreads]),
+                                  __fsub_rn(yk[2 * kLimbThreads], yi[2 * kLimbThreads]));
+        if (d > 0.0f && d <= FLT_MAX) r = __fsub_rn(d, tg);
+      }
+      resid[me * L + l] = r;
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int i = lane; i < total; i += kLimbThreads) {
+    const int p = i / row, r = i - p * row, j = r / 5, c = r - j * 5;
+    fitted[g0 + i] = c < 3 ? s_y[(j * 3 + c) * kLimbThreads + p] : poses[g0 + i];
+  }
+}
+
 // ---- person re-identification (ABI 20): a gallery of retired tracks per sequence -----------------------------------------
 // The definition is in include/fvp.h.  One workgroup of 256 threads per sequence walks the batch's frames in order and skips
 // the frames of other sequences, as k_track_update does.  Thread (p, bin) = tid owns counter (p, bin) of EVERY slot and gallery
@@ -867,6 +1098,55 @@ extern "C" int fvp_track_smooth(const float* fused_poses, const int32_t* frame_s
                      fused_poses, frame_set, ids, slots, joint_conf, flt_pose, flt_vel, flt_id, flt_age, smooth,
                      track_poses, track_state, B, N, J, nseq, T, rate_hz, min_cutoff, beta, d_cutoff, conf_min, damp,
                      max_age);
+  return launch_status();
+}
+
+// the checks of the limb table both limb exports share (behind their limit checks: L <= FVP_LIMB_MAX); the pairs go into prm
+static int limb_table(const int32_t* limbs, int L, int J, LimbPrm& prm) {
+  for (int l = 0; l < L; ++l) {
+    const int i = limbs[2 * l], k = limbs[2 * l + 1];
+    FVP_REQUIRE(i >= 0 && i < J && k >= 0 && k < J && i != k);
+    prm.limb[l][0] = uint8_t(i);
+    prm.limb[l][1] = uint8_t(k);
+  }
+  return 0;
+}
+
+extern "C" int fvp_limb_learn(const float* fused_poses, const int32_t* frame_set, const int32_t* ids, const int32_t* slots,
+                              const float* joint_conf, const int32_t* limbs, int L, float* limb_len, float* limb_var,
+                              int32_t* limb_cnt, int32_t* limb_out, int32_t* limb_id, float* target, float* limb_obs,
+                              int32_t* limb_state, int B, int N, int J, int nseq, int T, float conf_min, int min_frames,
+                              int window, float gate_sigma, float gate_mm, int relearn, fvp_stream_t s) {
+  FVP_REQUIRE(fused_poses && ids && slots && limbs && limb_len && limb_var && limb_cnt && limb_out && limb_id);
+  FVP_REQUIRE(target && limb_obs && limb_state);
+  FVP_REQUIRE(B >= 0 && N > 0 && J > 0 && L > 0 && nseq > 0 && T >= N);
+  FVP_REQUIRE(min_frames >= 1 && window >= min_frames && relearn >= 0);
+  FVP_REQUIRE(gate_sigma >= 0.0f && gate_mm >= 0.0f);          // written so that a NaN fails
+  FVP_LIMIT(L <= FVP_LIMB_MAX && J <= FVP_MAX_JOINTS && N <= kTrackDets && T <= kTrackSlots);
+  LimbPrm prm = {};
+  if (const int rc = limb_table(limbs, L, J, prm)) return rc;
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_limb_learn, dim3(ceil_div(T, kLimbThreads / L), nseq), dim3(kLimbThreads), 0, as_stream(s),
+                     fused_poses, frame_set, ids, slots, joint_conf, prm, L, limb_len, limb_var, limb_cnt, limb_out, limb_id,
+                     target, limb_obs, limb_state, B, N, J, nseq, T, conf_min, min_frames, window, gate_sigma, gate_mm,
+                     relearn);
+  return launch_status();
+}
+
+extern "C" int fvp_limb_fit(const float* poses, const int32_t* ids, const float* joint_conf, const float* target,
+                            const int32_t* limbs, int L, float* fitted, float* resid, int B, int N, int J, float conf_min,
+                            float stiffness, int iters, fvp_stream_t s) {
+  FVP_REQUIRE(poses && target && limbs && fitted);
+  FVP_REQUIRE(B >= 0 && N > 0 && J > 0 && L > 0 && iters >= 1 && iters <= 32);
+  FVP_REQUIRE(stiffness >= 0.0f && stiffness <= 1.0f);          // written so that a NaN fails
+  FVP_LIMIT(L <= FVP_LIMB_MAX && J <= FVP_MAX_JOINTS && N <= kTrackDets);
+  LimbPrm prm = {};
+  if (const int rc = limb_table(limbs, L, J, prm)) return rc;
+  if (B == 0) return 0;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_limb_fit, dim3(ceil_div(B * N, kLimbThreads)), dim3(kLimbThreads), 0, as_stream(s), poses, ids,
+                     joint_conf, target, prm, L, fitted, resid, B * N, J, conf_min, stiffness, iters);
   return launch_status();
 }
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 21
+#define FVP_ABI_VERSION 22
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -37,6 +37,14 @@ extern "C" {
 #define FVP_SIG_MAX_SAMPLES 16384 /* samples of one person in one frame: FVP_MAX_VIEWS * 64 limbs * 32 samples */
 #define FVP_REID_MAX_GALLERY 64 /* fvp_track_reid: gallery entries per sequence (G) */
 #define FVP_REID_MAX_WINDOW 1024 /* fvp_track_reid: frames a signature accumulates before it is halved (window) */
+#define FVP_LIMB_MAX 64          /* fvp_limb_learn, fvp_limb_fit: limbs of the table (L) */
+/* fvp_limb_learn: limb_state */
+#define FVP_LIMB_LEARNED 1       /* the sample was accepted and the limb has min_frames samples: target is its length */
+#define FVP_LIMB_LEARNING 2      /* the sample was accepted, fewer than min_frames so far: target is 0 */
+#define FVP_LIMB_NOT_MEASURED 0  /* an end is unsupported, or the ends coincide / overflow: the statistics are unchanged */
+#define FVP_LIMB_OUTLIER (-1)    /* the sample failed the gate: the statistics are unchanged, the outlier count grew */
+#define FVP_LIMB_RELEARNED (-2)  /* more than `relearn` outliers in a row: the limb starts over from this sample */
+#define FVP_LIMB_INVALID (-3)    /* an invalid slot, or a frame of no sequence */
 #define FVP_VIS_MAX_PEOPLE 32  /* fvp_joint_visibility: person slots per frame (N) */
 #define FVP_VIS_MAX_PRIMS 64    /* fvp_joint_visibility: body primitives per person (L) */
 #define FVP_TRI_MAX_RADIUS 8    /* fvp_triangulate_joints: window half-size in heat-map cells */
@@ -222,6 +230,79 @@ int fvp_track_smooth(const float* fused_poses, const int32_t* frame_set, const i
                      int32_t* track_state /* [B,T,2] */, int B, int N, int J, int nseq, int T, float rate_hz,
                      float min_cutoff, float beta, float d_cutoff, float conf_min, float damp, int max_age,
                      fvp_stream_t s);
+
+/* ---- limb model (ABI 22): bone lengths per person, and poses constrained to them -----------------------------------------
+ * The tracker, the smoother and re-ID treat every joint on its own; a person is a rigid linkage.  fvp_limb_learn keeps a
+ * running, gated estimate of every limb's length per track (from the frames in which both ends are supported);
+ * fvp_limb_fit moves a pose, as little as a few Gauss-Seidel sweeps allow, onto those lengths: with both ends supported each
+ * takes half of a limb's correction, an unsupported end takes all of it.  Both are fp32 with every operation rounded on
+ * its own; sums and products are evaluated exactly as written below; `/` and sqrtf are the correctly rounded forms.
+ * limbs is a HOST array [L][2] of joint index pairs (i, k), copied into the launch; any list works (COCO-17 has cycles),
+ * no tree is required.
+ * SUPPORTED: joint j of slot (b, n) is supported when (joint_conf is NULL or joint_conf[b][n][j] >= conf_min) and
+ * fabsf(x_c) <= FLT_MAX for its three coordinates (a NaN or Inf never is).
+ * dist(i, k): delta_c = x_k,c - x_i,c;  d = sqrtf((delta_0*delta_0 + delta_1*delta_1) + delta_2*delta_2);  d is VALID when
+ * d > 0 && d <= FLT_MAX.
+ *
+ * fvp_limb_learn.  State per sequence s, in caller-owned DEVICE memory, read and rewritten by every call:
+ *   limb_len, limb_var [nseq][T][L] fp32 (mm, mm^2), limb_cnt, limb_out [nseq][T][L] int32 (accepted samples, capped at
+ *   window; outliers in a row), all initially 0;  limb_id [nseq][T] int32, initially -1.
+ * Inputs per call: fused_poses [B][N][J][5]; frame_set [B] (NULL = sequence 0); ids [B][N] and slots [B][N] as
+ * fvp_track_update wrote them for the same batch; joint_conf [B][N][J] or NULL.
+ * Frames are consumed in batch order, sequences are independent.  A frame whose frame_set entry is outside [0, nseq)
+ * changes no state, and its outputs are written as invalid.  For frame b of sequence s, every track slot t:
+ *   1. n = the lowest detection slot with ids[b][n] >= 0 and slots[b][n] == t (a slot with ids >= 0 whose slots entry is
+ *      outside [0, T) is treated like one with ids < 0 everywhere below).  No n: the slot's state is untouched - the
+ *      lengths survive coasting and the tracker's freeing of the slot; only a new id resets them;
+ *   2. n exists and limb_id[s][t] != ids[b][n]: limb_id = ids[b][n], and len = var = 0, cnt = out = 0 for every limb;
+ *      step 3 follows in the same frame;
+ *   3. every limb l = (i, k) on its own, from fused_poses[b][n]:
+ *        either end unsupported, or d = dist(i, k) not VALID: NOT_MEASURED, limb_obs = (-1, 0), statistics unchanged;
+ *        else e = d - len, and the gate: when cnt >= min_frames, tol = fmaxf(gate_sigma * sqrtf(var), gate_mm) and the
+ *        sample passes when fabsf(e) <= tol; when cnt < min_frames it passes;
+ *        failed: out += 1; if out > relearn the limb starts over from this sample - len = d, var = 0, cnt = 1, out = 0,
+ *          RELEARNED - otherwise OUTLIER and len, var, cnt are unchanged;
+ *        passed: out = 0; c = min(cnt + 1, window); cnt = c; g = 1.0f / (float)c; len = len + g * e;
+ *          var = var + g * (e * (d - len) - var) with the NEW len (Welford up to window, exponential forgetting after it;
+ *          the first sample gives len = d, var = 0 without a special case); LEARNED when c >= min_frames, else LEARNING;
+ *        measured limbs write limb_obs = (d, e);
+ *        target[b][n][l] = len after this frame when cnt (after this frame) >= min_frames, else 0 - whatever the state;
+ *   4. an invalid slot (ids < 0) gets target = 0, limb_obs = (-1, 0), limb_state = INVALID.  (A further detection in the
+ *      same track slot, which fvp_track_update never writes, gets the values of the lowest one.)
+ * Outputs, every element written by every call: target [B][N][L] fp32, limb_obs [B][N][L][2] fp32 (d, e), limb_state
+ * [B][N][L] int32 (FVP_LIMB_*).  One thread per (s, t, l) walks the batch; one launch per batch.
+ *
+ * fvp_limb_fit is stateless, per slot (b, n).  The slot is valid when poses[b][n][0][3] >= 0 and (ids is NULL or
+ * ids[b][n] >= 0); an invalid slot is copied unchanged and its resid is 0.  Otherwise y = the xyz of poses[b][n], m_j =
+ * SUPPORTED decided once from the input pose, and for it = 0..iters-1, for l = 0..L-1 in table order, with l = (i, k):
+ *   t = target[b][n][l]; skip unless t > 0 (a NaN skips);  delta = y_k - y_i, d = dist;  skip unless d is VALID (a
+ *   non-finite joint constrains nothing and poisons nothing);
+ *   s = (stiffness * (d - t)) / d;  (w_i, w_k) = (0.5f, 0.5f) when m_i == m_k, (0, 1) when only i is supported, (1, 0)
+ *   when only k is;  y_i,c = y_i,c + (w_i * s) * delta_c;  y_k,c = y_k,c - (w_k * s) * delta_c.
+ * fitted [B][N][J][5]: y in columns 0:3, columns 3:5 copied (fitted may be poses itself);  resid [B][N][L] or NULL: d - t
+ * recomputed after the last sweep for the limbs with t > 0 and a VALID d, else 0.  poses may be any poses of the layout
+ * (fvp_track_smooth's smooth).  One lane per slot; one launch.
+ *
+ * Not built: carrying a person's lengths across re-identification, lengths as a re-ID or association cue, joint-angle
+ * limits, left/right symmetry, a fit coupled into the One-Euro state.
+ * FVP_EINVAL: a null required pointer (frame_set, joint_conf, fvp_limb_fit's ids and resid excepted); N, J, L or nseq < 1;
+ * T < N; a limb index outside [0, J) or i == k; min_frames < 1; window < min_frames; relearn < 0; gate_sigma or gate_mm not
+ * >= 0; stiffness outside [0, 1]; iters outside [1, 32] (a NaN fails every one of these comparisons).  FVP_ELIMIT: L >
+ * FVP_LIMB_MAX, J > FVP_MAX_JOINTS, N > FVP_TRACK_MAX_DETS, T > FVP_TRACK_MAX_TRACKS.  Nothing is written when an error is
+ * returned.  B == 0 returns 0 without a launch. */
+int fvp_limb_learn(const float* fused_poses /* [B][N][J][5] */, const int32_t* frame_set /* [B] or NULL */,
+                   const int32_t* ids, const int32_t* slots /* [B][N], fvp_track_update's */,
+                   const float* joint_conf /* [B][N][J] or NULL */, const int32_t* limbs /* HOST [L][2] */, int L,
+                   float* limb_len, float* limb_var, int32_t* limb_cnt, int32_t* limb_out /* state [nseq][T][L] */,
+                   int32_t* limb_id /* state [nseq][T], initially -1; the others 0 */,
+                   float* target /* [B][N][L] */, float* limb_obs /* [B][N][L][2] */, int32_t* limb_state /* [B][N][L] */,
+                   int B, int N, int J, int nseq, int T, float conf_min, int min_frames, int window,
+                   float gate_sigma, float gate_mm, int relearn, fvp_stream_t s);
+int fvp_limb_fit(const float* poses /* [B][N][J][5] */, const int32_t* ids /* [B][N] or NULL */,
+                 const float* joint_conf /* [B][N][J] or NULL */, const float* target /* [B][N][L] */,
+                 const int32_t* limbs /* HOST [L][2] */, int L, float* fitted /* [B][N][J][5] */,
+                 float* resid /* [B][N][L] or NULL */, int B, int N, int J, float conf_min, float stiffness, int iters,
+                 fvp_stream_t s);
 
 /* ---- person re-identification (ABI 20): old identities back after a gap -------------------------------------------------
  * fvp_track_update forgets a track after max_age frames: a person who leaves the capture volume, stays hidden for longer, or

@@ -20,6 +20,13 @@
 
 namespace fvp {
 
+// A joint is stamped, and counts for its person's extent, when both quotients are finite (a NaN or an Inf fails the compare)
+__device__ __forceinline__ bool ras_finite(double x, double y) {
+  const double big = 1.7976931348623157e308;          // DBL_MAX
+  return fabs(x) <= big && fabs(y) <= big;
+}
+constexpr double kRasBig = 1073741824.0;              // 2^30: window corners and lengths are clamped to it before int()
+
 __global__ void __launch_bounds__(256)
 k_rasterise(const double* __restrict__ joints, const int* __restrict__ num_people, int P, int J, int W, int H, int RB,
             double fsx, double fsy, double sigma, float* __restrict__ nchw, float* __restrict__ cl, int JP) {
@@ -40,14 +47,17 @@ k_rasterise(const double* __restrict__ joints, const int* __restrict__ num_peopl
   }
   __syncthreads();
   if (t < np_) {
-    // compute_human_scale (:197-203) with every joint visible
+    // compute_human_scale (:197-203) with every FINITE joint visible (include/fvp.h: a joint with a NaN or an Inf is left out)
     const double(*qp)[2] = q + t * J;
-    double minx = qp[0][0], maxx = minx, miny = qp[0][1], maxy = miny;
-    for (int k = 1; k < J; ++k) {
-      minx = fmin(minx, qp[k][0]);
-      maxx = fmax(maxx, qp[k][0]);
-      miny = fmin(miny, qp[k][1]);
-      maxy = fmax(maxy, qp[k][1]);
+    double minx = 0, maxx = 0, miny = 0, maxy = 0;
+    bool any = false;
+    for (int k = 0; k < J; ++k) {
+      if (!ras_finite(qp[k][0], qp[k][1])) continue;
+      minx = any ? fmin(minx, qp[k][0]) : qp[k][0];
+      maxx = any ? fmax(maxx, qp[k][0]) : qp[k][0];
+      miny = any ? fmin(miny, qp[k][1]) : qp[k][1];
+      maxy = any ? fmax(maxy, qp[k][1]) : qp[k][1];
+      any = true;
     }
     const double ext = fmax(maxy - miny, maxx - minx);
     double hs = ext * ext;
@@ -56,20 +66,28 @@ k_rasterise(const double* __restrict__ joints, const int* __restrict__ num_peopl
     const double cur_sigma = sigma * sqrt(hs / (96.0 * 96.0));
     const double tmp_size = cur_sigma * 3;
     const double size = 2 * tmp_size + 1;
-    prm[t][0] = tmp_size;
+    prm[t][0] = any ? tmp_size : -1.0;                // no finite joint: the person stamps nothing
     prm[t][1] = floor(size / 2);                      // x0 = y0 = size // 2
     prm[t][2] = 2 * (cur_sigma * cur_sigma);
-    prm[t][3] = ceil(size);                           // len(np.arange(0, size, 1))
+    prm[t][3] = fmin(ceil(size), kRasBig);            // len(np.arange(0, size, 1))
   }
   for (int n = 0; n < np_; ++n) {
     __syncthreads();                                  // parameters ready; previous person's LDS stores done
     const double tmp_size = prm[n][0], x0 = prm[n][1], den = prm[n][2];
+    if (!(tmp_size >= 0)) continue;                   // uniform over the workgroup
     const int ng = int(prm[n][3]);
     for (int j = wave; j < J; j += 4) {
-      const int mu_x = int(q[n * J + j][0]), mu_y = int(q[n * J + j][1]);           // trunc toward zero, as int()
-      const int ul0 = int(mu_x - tmp_size), ul1 = int(mu_y - tmp_size);
-      const int br0 = int(mu_x + tmp_size + 1), br1 = int(mu_y + tmp_size + 1);
-      if (ul0 >= W || ul1 >= H || br0 < 0 || br1 < 0) continue;
+      const double qx = q[n * J + j][0], qy = q[n * J + j][1];
+      if (!ras_finite(qx, qy)) continue;
+      // Python's int() truncates toward zero and never overflows: the window is placed in float64 (trunc() of a double is
+      // exact, and so is float(int(q))), and only a window that meets the image - corners within 2 tmp_size + 2 of it - is
+      // converted to int.  No NaN or Inf reaches a conversion (sigma and the strides are finite: host-checked).
+      const double mu_x = trunc(qx), mu_y = trunc(qy);
+      const double dul0 = trunc(mu_x - tmp_size), dul1 = trunc(mu_y - tmp_size);
+      const double dbr0 = trunc(mu_x + tmp_size + 1), dbr1 = trunc(mu_y + tmp_size + 1);
+      if (dul0 >= W || dul1 >= H || dbr0 < 0 || dbr1 < 0) continue;
+      const int ul0 = int(fmax(dul0, -kRasBig)), ul1 = int(fmax(dul1, -kRasBig));
+      const int br0 = int(fmin(dbr0, kRasBig)), br1 = int(fmin(dbr1, kRasBig));
       const int gx0 = ul0 < 0 ? -ul0 : 0, gx1 = (br0 < W ? br0 : W) - ul0;
       const int gy0 = ul1 < 0 ? -ul1 : 0, gy1 = (br1 < H ? br1 : H) - ul1;
       const int ix0 = ul0 > 0 ? ul0 : 0, iy0 = ul1 > 0 ? ul1 : 0;
@@ -725,6 +743,7 @@ extern "C" int fvp_rasterise_heatmaps(const double* joints, const int32_t* num_p
                                       float* heat_nchw, float* heat_cl, int JP, fvp_stream_t s) {
   FVP_REQUIRE(joints && num_people && (heat_nchw || heat_cl) && nimg >= 0 && P >= 0 && J > 0 && W > 0 && H > 0);
   FVP_REQUIRE(feat_stride_x > 0 && feat_stride_y > 0 && sigma > 0 && (!heat_cl || JP >= J));
+  FVP_REQUIRE(std::isfinite(feat_stride_x) && std::isfinite(feat_stride_y) && std::isfinite(sigma));
   if (nimg == 0) return 0;
   FVP_LIMIT(size_t(J) * W * sizeof(float) <= 32 * 1024 && P <= 64 && P * J <= 1024);
   int RB = 4;                                          // rows per band: the band of all joints fits 64 KB of LDS

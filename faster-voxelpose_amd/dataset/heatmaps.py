@@ -14,13 +14,28 @@ import torch
 from .. import _capi as capi
 
 
+def _is_batched(pred_pose2d):
+    """One frame is [view][person] of [J, >=2] people, a batch [frame][view][person].  The elements two levels down decide:
+    a view of a batch is a list (an empty one included - a person has at least one joint row) whose first element is a
+    2-D person; a person of a single frame is an array, or a nested list whose first element is a 1-D joint row.  With
+    nothing two levels down (a frame whose views are all empty) the input is one frame."""
+    for outer in pred_pose2d:
+        for x in outer:
+            if not isinstance(x, (list, tuple)):
+                return False                          # an array / tensor: a person
+            if len(x) == 0:
+                return True                           # an empty view
+            return np.ndim(x[0]) >= 2
+    return False
+
+
 def generate_input_heatmaps(pred_pose2d, resize_transform, cfg, sigma=None, device=None, channels_last=False,
                             _lib=None):
     """``pred_pose2d``: one frame = list over views of lists of ``[J, >=2]`` arrays (ORIGINAL image
     pixels, ``db_rec['pred_pose2d']``), or a list of such frames.  Returns ``[V,J,H,W]`` (or
     ``[B,V,J,H,W]``) float32 on ``device``; with ``channels_last=True`` also the ``[.., H*W, JP]``
     staging copy the projection kernels read."""
-    batched = len(pred_pose2d) > 0 and len(pred_pose2d[0]) > 0 and isinstance(pred_pose2d[0][0], (list, tuple))
+    batched = _is_batched(pred_pose2d)
     frames = pred_pose2d if batched else [pred_pose2d]
     device = torch.device(device if device is not None else cfg.DEVICE)
     lib = _lib if _lib is not None else capi.load()

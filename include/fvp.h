@@ -617,7 +617,17 @@ int fvp_fuse_poses(const float* pose2d, const float* pmax, const float* wgt, con
  * [nimg][J][H][W] (heat_nchw, the reference layout) and / or the channels-last staging copy
  * [nimg][H*W][JP] the projection kernels read (heat_cl; either may be NULL).  Replaces
  * JointsDataset.generate_input_heatmap (lib/dataset/JointsDataset.py:271-338, eval branch) and
- * compute_human_scale (:197-203); float64 scalar arithmetic like numpy, one rounding to fp32. */
+ * compute_human_scale (:197-203); float64 scalar arithmetic like numpy, one rounding to fp32.
+ * Counts: image i stamps its first min(max(num_people[i], 0), P) people; a count above P is clamped, a negative one is an
+ * empty image.  Every requested output element is written (+0.0 where nothing is stamped, and in the channels J..JP-1).
+ * Non-finite joints: a joint with a coordinate that is not finite (fabs(x) <= DBL_MAX fails for the coordinate or for its
+ * quotient by the stride: NaN, +-Inf) stamps nothing and is left out of its person's extent in compute_human_scale; a
+ * person with no finite joint stamps nothing.  (The reference raises in int(nan).)  Finite coordinates of any magnitude
+ * behave as the reference's Python integers do: a window beyond the image is skipped.
+ * FVP_EINVAL: null joints or num_people; both outputs null; nimg or P < 0; J, W or H < 1; a stride or sigma that is not
+ * > 0 or not finite; JP < J with heat_cl set.  nimg == 0 returns 0 before any limit check and writes nothing.
+ * FVP_ELIMIT: J * W * 4 > 32 KB (one row of all joints in LDS), P > 64, P * J > 1024.  Nothing is written when an error is
+ * returned. */
 int fvp_rasterise_heatmaps(const double* joints, const int32_t* num_people, int nimg, int P, int J, int W, int H,
                            double feat_stride_x, double feat_stride_y, double sigma, float* heat_nchw,
                            float* heat_cl, int JP, fvp_stream_t s);

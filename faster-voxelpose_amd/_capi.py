@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 22          # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 23          # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -38,6 +38,8 @@ BB_OUT_HEAT = 8
 BB_STEM = 16
 INGEST_SWAP_RB, INGEST_GENERAL = 1, 2
 YUV_BT601_LIMITED, YUV_BT709_LIMITED, YUV_BT601_FULL, YUV_BT709_FULL = 0, 1, 2, 3
+ANON_RECT, ANON_ELLIPSE = 0, 1
+ANON_MOSAIC, ANON_FILL = 0, 1
 
 
 class FvpGeom(C.Structure):
@@ -125,6 +127,9 @@ SIGNATURES = {
     "fvp_crop_rois": [_P, _I, _I, _I, _P, _I, _I, C.POINTER(_F), C.POINTER(_F), _I, _I, _I, _P, _P, _P],
     "fvp_crop_rois_nv12": [_P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, _P, _I, _I, C.POINTER(_F),
                            C.POINTER(_F), _I, _I, _P, _P, _P],
+    "fvp_anonymise_rois": [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_uint8), _P],
+    "fvp_anonymise_rois_nv12": [_P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, _P, _I, _I, _I, _I, _I,
+                                C.POINTER(C.c_uint8), _P],
     "fvp_joint_visibility": [_P, _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(_F), _I, _F, _I, _I, _P, _P,
                              _P, _P],
     "fvp_triangulate_joints": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _G, _I, _F, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],

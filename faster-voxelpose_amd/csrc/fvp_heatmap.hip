@@ -501,6 +501,281 @@ k_draw_poses_nv12(uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, DrawNv12P
   *pc = uint16_t(unsigned(u) | (unsigned(v) << 8));
 }
 
+// ---- faces out of the camera frames (fvp_anonymise_rois, fvp_anonymise_rois_nv12; include/fvp.h, ABI 23) --------------------
+// The second pair of kernels that WRITE frames.  A workgroup owns a 64 x 32 pixel tile of one frame - whole cells for every
+// permitted cell size (2 .. 32), cells being anchored at the frame's origin.  Thread k < rois_per_frame loads ROI k of the
+// frame, derives the ellipse's terms and decides whether the ROI can cover a pixel of the tile (RECT: the box against the
+// tile's pixel centres; ELLIPSE: the tile pixel nearest the centre - every fp32 operation of the coverage test is monotone in
+// |dx| and in |dy|, so that pixel is covered whenever any pixel of the tile is); a tile no ROI meets leaves, uniformly, before
+// any frame address is formed.  Otherwise: coverage of the thread's pixels (a bit per pixel, in registers), the touched cells
+// marked in LDS, barrier, the ORIGINAL bytes of every in-frame pixel of a touched cell summed into LDS (integer adds commute:
+// the sums do not depend on the schedule), barrier, the covered pixels written.  IN PLACE IS SAFE BECAUSE every read of a cell
+// precedes that last barrier, every write follows it, and both happen in the one workgroup that owns the cell; no two
+// workgroups touch the same byte.  FILL reads no frame byte and needs neither LDS sums nor the two barriers.
+constexpr int kAnonTW = 64, kAnonTH = 32, kAnonThreads = 256, kAnonMaxRois = 64;
+constexpr int kAnonRows = kAnonTH / (kAnonThreads / kAnonTW);                         // pixels (rows) per thread, RGB
+constexpr int kAnonMaxCells = (kAnonTW / 2) * (kAnonTH / 2);                          // cell == 2
+
+struct AnonLds {
+  float box[kAnonMaxRois][4];                          // x0, y0, x1, y1
+  float ell[kAnonMaxRois][5];                          // cx, cy, hw * hw, hh * hh, (hw * hw) * (hh * hh)
+  int meets[kAnonMaxRois];                             // active, and may cover a pixel of this tile
+  int touched[kAnonMaxCells];
+  int sum[kAnonMaxCells][3];                           // R, G, B or Y, U, V
+};
+
+// include/fvp.h, "Coverage"; this TU is compiled with -ffp-contract=off: every * + - is rounded on its own
+__device__ __forceinline__ bool anon_covers(const AnonLds& s, int k, int shape, float xc, float yc) {
+  if (shape == FVP_ANON_RECT) return s.box[k][0] <= xc && xc < s.box[k][2] && s.box[k][1] <= yc && yc < s.box[k][3];
+  const float dx = xc - s.ell[k][0], dy = yc - s.ell[k][1];
+  return (dx * dx) * s.ell[k][3] + (dy * dy) * s.ell[k][2] <= s.ell[k][4];
+}
+
+// Before the first barrier: thread k takes ROI k of frame f against the tile's in-frame pixels [tx0, tx1] x [ty0, ty1]
+__device__ __forceinline__ void anon_begin(AnonLds& s, int tid, const float* __restrict__ rois, int f, int rpf, int shape,
+                                           int tx0, int ty0, int tx1, int ty1) {
+  if (tid >= rpf) return;
+  const float* r = rois + 4 * (long(f) * rpf + tid);
+  const float x0 = r[0], y0 = r[1], x1 = r[2], y1 = r[3];
+  const float big = 65536.0f;                            // a NaN or an Inf fails the compare
+  const bool active = fabsf(x0) <= big && fabsf(y0) <= big && fabsf(x1) <= big && fabsf(y1) <= big && x1 > x0 && y1 > y0;
+  const float cx = (x0 + x1) * 0.5f, cy = (y0 + y1) * 0.5f, hw = (x1 - x0) * 0.5f, hh = (y1 - y0) * 0.5f;
+  const float hw2 = hw * hw, hh2 = hh * hh;
+  s.box[tid][0] = x0;
+  s.box[tid][1] = y0;
+  s.box[tid][2] = x1;
+  s.box[tid][3] = y1;
+  s.ell[tid][0] = cx;
+  s.ell[tid][1] = cy;
+  s.ell[tid][2] = hw2;
+  s.ell[tid][3] = hh2;
+  s.ell[tid][4] = hw2 * hh2;
+  bool meets = false;
+  if (active) {
+    if (shape == FVP_ANON_RECT) {
+      meets = x1 > float(tx0) + 0.5f && x0 <= float(tx1) + 0.5f && y1 > float(ty0) + 0.5f && y0 <= float(ty1) + 0.5f;
+    } else {                                             // |cx|, |cy| <= 65536: the conversions are exact
+      const int fx = int(floorf(cx)), fy = int(floorf(cy));
+      const int xn = fx < tx0 ? tx0 : fx > tx1 ? tx1 : fx, yn = fy < ty0 ? ty0 : fy > ty1 ? ty1 : fy;
+      const float dx = (float(xn) + 0.5f) - cx, dy = (float(yn) + 0.5f) - cy;
+      meets = (dx * dx) * hh2 + (dy * dy) * hw2 <= hw2 * hh2;
+    }
+  }
+  s.meets[tid] = meets ? 1 : 0;
+}
+
+// m = (2 S + n) / (2 n): the mean of n bytes, half up; S <= 1024 * 255
+__device__ __forceinline__ int anon_mean(int S, int n) { return (2 * S + n) / (2 * n); }
+
+// in-frame pixels of the cell that holds pixel p along an axis of extent `size`
+__device__ __forceinline__ int anon_extent(int p, int sh, int size) {
+  const int a = (p >> sh) << sh, b = a + (1 << sh);
+  return (b < size ? b : size) - a;
+}
+
+__global__ void __launch_bounds__(kAnonThreads)
+k_anonymise_rois(uint8_t* __restrict__ frames, int Hs, int Ws, const float* __restrict__ rois, int rpf, int sh, int shape,
+                 int mode, unsigned colour) {
+  __shared__ AnonLds s;
+  const int tid = threadIdx.x, f = blockIdx.z;
+  const int tx0 = blockIdx.x * kAnonTW, ty0 = blockIdx.y * kAnonTH;
+  const int tx1 = (tx0 + kAnonTW < Ws ? tx0 + kAnonTW : Ws) - 1, ty1 = (ty0 + kAnonTH < Hs ? ty0 + kAnonTH : Hs) - 1;
+  anon_begin(s, tid, rois, f, rpf, shape, tx0, ty0, tx1, ty1);
+  __syncthreads();
+  const int lx = tid & (kAnonTW - 1), ly = tid / kAnonTW;        // this thread's pixels: (lx, ly + 4 r) of the tile
+  const int x = tx0 + lx;
+  const float xc = float(x) + 0.5f;
+  unsigned cov = 0u;
+  bool any = false;
+  for (int k = 0; k < rpf; ++k) {
+    if (!s.meets[k]) continue;                         // uniform over the workgroup
+    any = true;
+#pragma unroll
+    for (int r = 0; r < kAnonRows; ++r)
+      if (anon_covers(s, k, shape, xc, float(ty0 + ly + 4 * r) + 0.5f)) cov |= 1u << r;
+  }
+  if (!any) return;                                    // uniform: no frame address has been formed
+#pragma unroll
+  for (int r = 0; r < kAnonRows; ++r)
+    if (x >= Ws || ty0 + ly + 4 * r >= Hs) cov &= ~(1u << r);
+  uint8_t* fr = frames + size_t(f) * Hs * Ws * 3;
+  if (mode == FVP_ANON_FILL) {
+#pragma unroll
+    for (int r = 0; r < kAnonRows; ++r)
+      if ((cov >> r) & 1u) {
+        uint8_t* p = fr + (size_t(ty0 + ly + 4 * r) * Ws + x) * 3;
+        p[0] = uint8_t(colour & 255u);
+        p[1] = uint8_t((colour >> 8) & 255u);
+        p[2] = uint8_t((colour >> 16) & 255u);
+      }
+    return;
+  }
+  const int ncw = kAnonTW >> sh, cells = ncw * (kAnonTH >> sh);
+  for (int i = tid; i < cells; i += kAnonThreads) {
+    s.touched[i] = 0;
+    s.sum[i][0] = 0;
+    s.sum[i][1] = 0;
+    s.sum[i][2] = 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kAnonRows; ++r)
+    if ((cov >> r) & 1u) s.touched[((ly + 4 * r) >> sh) * ncw + (lx >> sh)] = 1;
+  __syncthreads();
+  {                                                    // a thread's pixels share a column: consecutive ones of a cell are summed in registers
+    int cur = -1, a0 = 0, a1 = 0, a2 = 0;
+#pragma unroll
+    for (int r = 0; r < kAnonRows; ++r) {
+      const int y = ty0 + ly + 4 * r, ci = ((ly + 4 * r) >> sh) * ncw + (lx >> sh);
+      if (x >= Ws || y >= Hs || !s.touched[ci]) continue;
+      if (ci != cur) {
+        if (cur >= 0) {
+          atomicAdd(&s.sum[cur][0], a0);
+          atomicAdd(&s.sum[cur][1], a1);
+          atomicAdd(&s.sum[cur][2], a2);
+        }
+        cur = ci;
+        a0 = a1 = a2 = 0;
+      }
+      const uint8_t* p = fr + (size_t(y) * Ws + x) * 3;
+      draw_note_read(p);
+      a0 += p[0];
+      a1 += p[1];
+      a2 += p[2];
+    }
+    if (cur >= 0) {
+      atomicAdd(&s.sum[cur][0], a0);
+      atomicAdd(&s.sum[cur][1], a1);
+      atomicAdd(&s.sum[cur][2], a2);
+    }
+  }
+  __syncthreads();                                     // every read of the tile's cells is behind us
+  if (cov == 0u) return;
+  const int cw = anon_extent(x, sh, Ws);
+#pragma unroll
+  for (int r = 0; r < kAnonRows; ++r)
+    if ((cov >> r) & 1u) {
+      const int y = ty0 + ly + 4 * r, ci = ((ly + 4 * r) >> sh) * ncw + (lx >> sh);
+      const int n = cw * anon_extent(y, sh, Hs);
+      uint8_t* p = fr + (size_t(y) * Ws + x) * 3;
+      p[0] = uint8_t(anon_mean(s.sum[ci][0], n));
+      p[1] = uint8_t(anon_mean(s.sum[ci][1], n));
+      p[2] = uint8_t(anon_mean(s.sum[ci][2], n));
+    }
+}
+
+// The same on an NV12 surface: the tile, the ROI list and the coverage test are those of k_anonymise_rois; a thread owns two
+// 2 x 2 luma quads (16 luma rows apart) and the (U, V) pair that serves each, as in k_draw_poses_nv12.  Cells and tiles start
+// at even coordinates and Hs, Ws are even: a quad lies in one cell, and inside the frame or outside it as a whole; the chroma
+// cell of a luma cell is the pairs of its quads.  Luma goes byte by byte, a pair as one 2-byte load and one 2-byte store.
+// `colour` holds (Yc, Uc, Vc).
+constexpr int kAnonQuads = (kAnonTW / 2) * (kAnonTH / 2) / kAnonThreads;              // quads per thread
+
+__global__ void __launch_bounds__(kAnonThreads)
+k_anonymise_rois_nv12(uint8_t* __restrict__ yp, uint8_t* __restrict__ uvp, DrawNv12Prm q, int Hs, int Ws,
+                      const float* __restrict__ rois, int rpf, int sh, int shape, int mode, unsigned colour) {
+  __shared__ AnonLds s;
+  const int tid = threadIdx.x, f = blockIdx.z;
+  const int tx0 = blockIdx.x * kAnonTW, ty0 = blockIdx.y * kAnonTH;
+  const int tx1 = (tx0 + kAnonTW < Ws ? tx0 + kAnonTW : Ws) - 1, ty1 = (ty0 + kAnonTH < Hs ? ty0 + kAnonTH : Hs) - 1;
+  anon_begin(s, tid, rois, f, rpf, shape, tx0, ty0, tx1, ty1);
+  __syncthreads();
+  const int lx = 2 * (tid & (kAnonTW / 2 - 1)), ly = 2 * (tid / (kAnonTW / 2));      // quad r: top-left (lx, ly + 16 r) of the tile
+  const int x = tx0 + lx;
+  unsigned cov = 0u;                                   // bit 4 r + e: pixel (x + (e & 1), y_r + (e >> 1))
+  bool any = false;
+  for (int k = 0; k < rpf; ++k) {
+    if (!s.meets[k]) continue;                         // uniform over the workgroup
+    any = true;
+#pragma unroll
+    for (int i = 0; i < 4 * kAnonQuads; ++i)
+      if (anon_covers(s, k, shape, float(x + (i & 1)) + 0.5f, float(ty0 + ly + 16 * (i >> 2) + ((i >> 1) & 1)) + 0.5f))
+        cov |= 1u << i;
+  }
+  if (!any) return;                                    // uniform: no surface address has been formed
+#pragma unroll
+  for (int r = 0; r < kAnonQuads; ++r)
+    if (x >= Ws || ty0 + ly + 16 * r >= Hs) cov &= ~(15u << (4 * r));
+  uint8_t* fy = yp + long(f) * q.y_frame;
+  uint8_t* fuv = uvp + long(f) * q.uv_frame;
+  if (mode == FVP_ANON_FILL) {
+#pragma unroll
+    for (int r = 0; r < kAnonQuads; ++r) {
+      const unsigned c4 = (cov >> (4 * r)) & 15u;
+      if (!c4) continue;
+      const int y = ty0 + ly + 16 * r;
+      uint8_t* pl = fy + long(y) * q.y_pitch + x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((c4 >> e) & 1u) pl[(e >> 1) * q.y_pitch + (e & 1)] = uint8_t(colour & 255u);
+      *reinterpret_cast<uint16_t*>(fuv + long(y >> 1) * q.uv_pitch + x) = uint16_t(colour >> 8);
+    }
+    return;
+  }
+  const int ncw = kAnonTW >> sh, cells = ncw * (kAnonTH >> sh);
+  for (int i = tid; i < cells; i += kAnonThreads) {
+    s.touched[i] = 0;
+    s.sum[i][0] = 0;
+    s.sum[i][1] = 0;
+    s.sum[i][2] = 0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kAnonQuads; ++r)
+    if ((cov >> (4 * r)) & 15u) s.touched[((ly + 16 * r) >> sh) * ncw + (lx >> sh)] = 1;
+  __syncthreads();
+  {
+    int cur = -1, a0 = 0, a1 = 0, a2 = 0;
+#pragma unroll
+    for (int r = 0; r < kAnonQuads; ++r) {
+      const int y = ty0 + ly + 16 * r, ci = ((ly + 16 * r) >> sh) * ncw + (lx >> sh);
+      if (x >= Ws || y >= Hs || !s.touched[ci]) continue;
+      if (ci != cur) {
+        if (cur >= 0) {
+          atomicAdd(&s.sum[cur][0], a0);
+          atomicAdd(&s.sum[cur][1], a1);
+          atomicAdd(&s.sum[cur][2], a2);
+        }
+        cur = ci;
+        a0 = a1 = a2 = 0;
+      }
+      const uint8_t* pl = fy + long(y) * q.y_pitch + x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint8_t* p = pl + (e >> 1) * q.y_pitch + (e & 1);
+        draw_note_read(p);
+        a0 += *p;
+      }
+      const uint8_t* pc = fuv + long(y >> 1) * q.uv_pitch + x;
+      draw_note_read(pc);
+      const unsigned w = *reinterpret_cast<const uint16_t*>(pc);
+      a1 += int(w & 255u);
+      a2 += int(w >> 8);
+    }
+    if (cur >= 0) {
+      atomicAdd(&s.sum[cur][0], a0);
+      atomicAdd(&s.sum[cur][1], a1);
+      atomicAdd(&s.sum[cur][2], a2);
+    }
+  }
+  __syncthreads();                                     // every read of the tile's cells is behind us
+  if (cov == 0u) return;
+  const int cw = anon_extent(x, sh, Ws);
+#pragma unroll
+  for (int r = 0; r < kAnonQuads; ++r) {
+    const unsigned c4 = (cov >> (4 * r)) & 15u;
+    if (!c4) continue;
+    const int y = ty0 + ly + 16 * r, ci = ((ly + 16 * r) >> sh) * ncw + (lx >> sh);
+    const int n = cw * anon_extent(y, sh, Hs);         // luma pixels of the cell; its pairs: n / 4
+    const int my = anon_mean(s.sum[ci][0], n), mu = anon_mean(s.sum[ci][1], n >> 2), mv = anon_mean(s.sum[ci][2], n >> 2);
+    uint8_t* pl = fy + long(y) * q.y_pitch + x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if ((c4 >> e) & 1u) pl[(e >> 1) * q.y_pitch + (e & 1)] = uint8_t(my);
+    *reinterpret_cast<uint16_t*>(fuv + long(y >> 1) * q.uv_pitch + x) = uint16_t(unsigned(mu) | (unsigned(mv) << 8));
+  }
+}
+
 // ---- person crops out (fvp_person_rois, fvp_crop_rois, fvp_crop_rois_nv12; include/fvp.h, ABI 16) -----------------------
 // One box per (frame, view, person) from the per-view pixels of fvp_joint_evidence: one thread per box walks the person's
 // joints in ascending order (min / max of the usable ones, their count, the sum of their heatmap samples).  A few hundred
@@ -851,37 +1126,97 @@ extern "C" int fvp_draw_poses(uint8_t* frames, int B, int V, int Hs, int Ws, con
   return launch_status();
 }
 
+// what the calls that write an NV12 surface in place (fvp_draw_poses_nv12, fvp_anonymise_rois_nv12) require of it; F frames
+static int nv12_write_args(const uint8_t* uv, long F, int Hs, int Ws, long y_pitch, long uv_pitch, long y_frame_stride,
+                           long uv_frame_stride, int standard) {
+  FVP_REQUIRE(Hs % 2 == 0 && Ws % 2 == 0 && y_pitch >= Ws && uv_pitch >= Ws);
+  // a (U, V) pair is one 2-byte load and one 2-byte store
+  FVP_REQUIRE(uv_pitch % 2 == 0 && uv_frame_stride % 2 == 0 && reinterpret_cast<uintptr_t>(uv) % 2 == 0);
+  FVP_REQUIRE(standard >= 0 && standard < 4);
+  FVP_REQUIRE(F <= 1 || (y_frame_stride >= (Hs - 1) * y_pitch + Ws && uv_frame_stride >= (Hs / 2 - 1) * uv_pitch + Ws));
+  return 0;
+}
+
+// R, G, B -> (Yc, Uc, Vc) of a standard, include/fvp.h; >> is arithmetic
+static void rgb_to_yuv(int standard, const uint8_t rgb[3], uint8_t yuv[3]) {
+  static const int coeffs[4][12] = {FVP_RGB2YUV_BT601_LIMITED_COEFFS, FVP_RGB2YUV_BT709_LIMITED_COEFFS,
+                                    FVP_RGB2YUV_BT601_FULL_COEFFS, FVP_RGB2YUV_BT709_FULL_COEFFS};
+  const int* k = coeffs[standard];
+  const int r = rgb[0], g = rgb[1], bl = rgb[2];
+  for (int c = 0; c < 3; ++c) {
+    const int v = k[4 * c] + ((k[4 * c + 1] * r + k[4 * c + 2] * g + k[4 * c + 3] * bl + 32768) >> 16);
+    yuv[c] = uint8_t(v < 0 ? 0 : v > 255 ? 255 : v);
+  }
+}
+
 extern "C" int fvp_draw_poses_nv12(uint8_t* y, uint8_t* uv, int B, int V, int Hs, int Ws, long y_pitch, long uv_pitch,
                                    long y_frame_stride, long uv_frame_stride, int standard, const float* views,
                                    const int32_t* ids, const float* joint_conf, int N, int J, const int32_t* limbs, int L,
                                    const uint8_t* palette, int P, int joint_radius_q4, int limb_half_q4, int alpha,
                                    float conf_min, fvp_stream_t s) {
-  static const int coeffs[4][12] = {FVP_RGB2YUV_BT601_LIMITED_COEFFS, FVP_RGB2YUV_BT709_LIMITED_COEFFS,
-                                    FVP_RGB2YUV_BT601_FULL_COEFFS, FVP_RGB2YUV_BT709_FULL_COEFFS};
   FVP_REQUIRE(y && uv);
   DrawPrm prm = {};
   if (const int rc = draw_args(B, V, Hs, Ws, views, N, J, limbs, L, palette, P, joint_radius_q4, limb_half_q4, alpha,
                                conf_min, prm))
     return rc;
-  FVP_REQUIRE(Hs % 2 == 0 && Ws % 2 == 0 && y_pitch >= Ws && uv_pitch >= Ws);
-  // a (U, V) pair is one 2-byte load and one 2-byte store
-  FVP_REQUIRE(uv_pitch % 2 == 0 && uv_frame_stride % 2 == 0 && reinterpret_cast<uintptr_t>(uv) % 2 == 0);
-  FVP_REQUIRE(standard >= 0 && standard < 4);
-  FVP_REQUIRE(long(B) * V <= 1 || (y_frame_stride >= (Hs - 1) * y_pitch + Ws && uv_frame_stride >= (Hs / 2 - 1) * uv_pitch + Ws));
-  const int* k = coeffs[standard];
-  for (int i = 0; i < P; ++i) {                        // palette entry -> (Yc, Uc, Vc), include/fvp.h; >> is arithmetic
-    const int r = palette[3 * i], g = palette[3 * i + 1], bl = palette[3 * i + 2];
-    for (int c = 0; c < 3; ++c) {
-      const int v = k[4 * c] + ((k[4 * c + 1] * r + k[4 * c + 2] * g + k[4 * c + 3] * bl + 32768) >> 16);
-      prm.pal[i][c] = uint8_t(v < 0 ? 0 : v > 255 ? 255 : v);
-    }
-  }
+  if (const int rc = nv12_write_args(uv, long(B) * V, Hs, Ws, y_pitch, uv_pitch, y_frame_stride, uv_frame_stride, standard))
+    return rc;
+  for (int i = 0; i < P; ++i) rgb_to_yuv(standard, palette + 3 * i, prm.pal[i]);
   if (long(B) * V == 0) return 0;
   const DrawNv12Prm q = {y_pitch, uv_pitch, y_frame_stride, uv_frame_stride};
   ProfScope ps(FVP_K_OTHER, as_stream(s));
   hipLaunchKernelGGL(k_draw_poses_nv12, dim3(ceil_div(Ws, kDrawTW), ceil_div(Hs, kDrawTH), unsigned(B * V)),
                      dim3(kDrawThreads), 0, as_stream(s), y, uv, q, V, Hs, Ws, views, ids, joint_conf, N, J, L, P, prm,
                      joint_radius_q4, limb_half_q4, alpha, conf_min);
+  return launch_status();
+}
+
+// argument checks both anonymiser exports share; the cell size goes out as its log2
+static int anon_args(int F, int Hs, int Ws, const float* rois, int R, int rois_per_frame, int cell, int shape, int mode,
+                     const uint8_t* colour, int& sh) {
+  FVP_REQUIRE(rois && F >= 0 && R >= 0 && Hs >= 1 && Ws >= 1);
+  FVP_REQUIRE(rois_per_frame >= 1 && long(R) == long(F) * rois_per_frame);
+  FVP_REQUIRE(cell == 2 || cell == 4 || cell == 8 || cell == 16 || cell == 32);
+  FVP_REQUIRE(shape == FVP_ANON_RECT || shape == FVP_ANON_ELLIPSE);
+  FVP_REQUIRE(mode == FVP_ANON_MOSAIC || (mode == FVP_ANON_FILL && colour));
+  FVP_LIMIT(rois_per_frame <= kAnonMaxRois && Hs <= 16384 && Ws <= 16384 && F <= 65535);
+  for (sh = 1; (1 << sh) < cell; ++sh) {
+  }
+  return 0;
+}
+
+extern "C" int fvp_anonymise_rois(uint8_t* frames, int F, int Hs, int Ws, const float* rois, int R, int rois_per_frame,
+                                  int cell, int shape, int mode, const uint8_t* colour, fvp_stream_t s) {
+  FVP_REQUIRE(frames);
+  int sh = 0;
+  if (const int rc = anon_args(F, Hs, Ws, rois, R, rois_per_frame, cell, shape, mode, colour, sh)) return rc;
+  if (R == 0) return 0;
+  const unsigned col = mode == FVP_ANON_FILL ? unsigned(colour[0]) | (unsigned(colour[1]) << 8) | (unsigned(colour[2]) << 16) : 0u;
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_anonymise_rois, dim3(ceil_div(Ws, kAnonTW), ceil_div(Hs, kAnonTH), unsigned(F)), dim3(kAnonThreads), 0,
+                     as_stream(s), frames, Hs, Ws, rois, rois_per_frame, sh, shape, mode, col);
+  return launch_status();
+}
+
+extern "C" int fvp_anonymise_rois_nv12(uint8_t* y, uint8_t* uv, int F, int Hs, int Ws, long y_pitch, long uv_pitch,
+                                       long y_frame_stride, long uv_frame_stride, int standard, const float* rois, int R,
+                                       int rois_per_frame, int cell, int shape, int mode, const uint8_t* colour,
+                                       fvp_stream_t s) {
+  FVP_REQUIRE(y && uv);
+  int sh = 0;
+  if (const int rc = anon_args(F, Hs, Ws, rois, R, rois_per_frame, cell, shape, mode, colour, sh)) return rc;
+  if (const int rc = nv12_write_args(uv, F, Hs, Ws, y_pitch, uv_pitch, y_frame_stride, uv_frame_stride, standard)) return rc;
+  if (R == 0) return 0;
+  unsigned col = 0u;
+  if (mode == FVP_ANON_FILL) {                           // converted once, on the host, as fvp_draw_poses_nv12 converts its palette
+    uint8_t yuv[3];
+    rgb_to_yuv(standard, colour, yuv);
+    col = unsigned(yuv[0]) | (unsigned(yuv[1]) << 8) | (unsigned(yuv[2]) << 16);
+  }
+  const DrawNv12Prm q = {y_pitch, uv_pitch, y_frame_stride, uv_frame_stride};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_anonymise_rois_nv12, dim3(ceil_div(Ws, kAnonTW), ceil_div(Hs, kAnonTH), unsigned(F)),
+                     dim3(kAnonThreads), 0, as_stream(s), y, uv, q, Hs, Ws, rois, rois_per_frame, sh, shape, mode, col);
   return launch_status();
 }
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 22
+#define FVP_ABI_VERSION 23
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -63,6 +63,11 @@ extern "C" {
 #define FVP_CAL_CLAMPED 2        /* solved, and scaled down to the trust region before it was applied */
 #define FVP_CAL_FEW 0            /* fewer than min_obs observations: the record is copied */
 #define FVP_CAL_DEGENERATE (-1)  /* the normal matrix is not positive definite enough, or the step is not finite: copied */
+/* fvp_anonymise_rois, fvp_anonymise_rois_nv12: shape and mode */
+#define FVP_ANON_RECT 0          /* the box itself */
+#define FVP_ANON_ELLIPSE 1       /* the ellipse inscribed in the box */
+#define FVP_ANON_MOSAIC 0        /* covered pixels take the mean of their frame-anchored cell */
+#define FVP_ANON_FILL 1          /* covered pixels take one colour */
 
 #define FVP_EINVAL 10001 /* bad argument (null pointer, unsupported size) */
 #define FVP_ELIMIT 10002 /* size beyond a compiled limit (see message) */
@@ -845,6 +850,65 @@ int fvp_crop_rois_nv12(const uint8_t* y, const uint8_t* uv, int F, int Hs, int W
                        int standard /* FVP_YUV_* */, const float* rois /* DEVICE [R][4] */, int R, int rois_per_frame,
                        const float mean[3], const float stdv[3], int h, int w, uint16_t* nhwc8, float* nchw,
                        fvp_stream_t s);
+
+/* ---- faces out of the camera frames (ABI 23): fvp_anonymise_rois, fvp_anonymise_rois_nv12 ---------------------------------
+ * A rig that records or shows its camera streams usually has to hide who is in them before a frame leaves the machine.
+ * fvp_person_rois makes a box from any joint subset, the head's included; fvp_crop_rois only cuts a copy out.  These two
+ * calls WRITE BACK: the pixels a list of boxes covers are replaced in place, by a mosaic or by one colour.
+ * fvp_anonymise_rois: frames [F][Hs][Ws][3] uint8, the contiguous HWC layout of fvp_ingest_frames / fvp_draw_poses.
+ * fvp_anonymise_rois_nv12: the surface of fvp_draw_poses_nv12 - y, uv, y_pitch, uv_pitch, y_frame_stride, uv_frame_stride
+ * (bytes) and standard with the same rules (Hs and Ws even, uv at an even address, even uv_pitch and uv_frame_stride), and
+ * THE CALLER GUARANTEES THAT THE TWO PLANES DO NOT OVERLAP, as there.
+ * rois [R][4] fp32 (x0, y0, x1, y1) in DEVICE memory, in pixels of the frame; R == F * rois_per_frame and ROI r belongs to
+ * frame r / rois_per_frame, as for fvp_crop_rois.  cell: 2, 4, 8, 16 or 32.  shape: FVP_ANON_RECT or FVP_ANON_ELLIPSE.  mode:
+ * FVP_ANON_MOSAIC or FVP_ANON_FILL.  colour [3] uint8 R, G, B: HOST memory, goes to the kernel by value, used by FILL only
+ * (it may be NULL for MOSAIC).
+ * Active ROI: all four values v satisfy fabsf(v) <= 65536.0f (an fp32 compare: a NaN or an Inf fails it), and x1 > x0 and
+ *   y1 > y0.  Any other ROI is inactive and covers nothing - the all-zero invalid box of fvp_person_rois is one.
+ * Coverage: pixel (x, y) has the centre xc = float(x) + 0.5f, yc = float(y) + 0.5f (both exact).  An active ROI covers it
+ *   RECT:     iff x0 <= xc && xc < x1 && y0 <= yc && yc < y1;
+ *   ELLIPSE:  with cx = (x0 + x1) * 0.5f, hw = (x1 - x0) * 0.5f, dx = xc - cx and cy = (y0 + y1) * 0.5f, hh = (y1 - y0) * 0.5f,
+ *             dy = yc - cy:   iff (dx*dx)*(hh*hh) + (dy*dy)*(hw*hw) <= (hw*hw)*(hh*hh)
+ *             in fp32, every operation rounded on its own (no fused multiply-add), evaluated as written.  There is no
+ *             division, and the bound of 65536 keeps every term finite (below 2^70).  The expression is taken literally
+ *             also where it underflows: a box thinner than about 1e-22 pixels both ways has hw*hw == hh*hh == 0 and covers
+ *             every pixel of its frame (0 <= 0); no box made from pixel coordinates is that thin.
+ *   A pixel is COVERED iff an active ROI of its frame covers it: a union - the order of the ROIs never matters.
+ * Cells: anchored at the frame's origin, not at a box.  Cell (i, j) is the pixels [i*cell, min((i+1)*cell, Ws)) x [j*cell,
+ *   min((j+1)*cell, Hs)); the last cells of a row / column may be narrower.  A frame-anchored mosaic does not shimmer when
+ *   a box moves by a pixel, and overlapping boxes agree on it.  A cell is TOUCHED iff one of its pixels is covered.
+ * MOSAIC, RGB: for a touched cell and each channel, S = the sum of the ORIGINAL bytes of ALL n in-frame pixels of the cell,
+ *   covered or not;  m = (2*S + n) / (2*n)  in int32 with truncating division (the mean, half up).  Every covered pixel of
+ *   the cell becomes m.  Uncovered pixels are not written; untouched cells are neither read nor written.
+ * MOSAIC, NV12: luma as above, one channel.  The chroma cell of luma cell (i, j) is its (cell/2) x (cell/2) block of (U, V)
+ *   pairs, clipped to (Ws/2) x (Hs/2).  A pair is covered iff any of the four luma pixels of its quad is covered; U and V of
+ *   a covered pair become the chroma cell's means, by the same formula over the original in-frame pairs of the cell.  A
+ *   chroma cell is read iff its luma cell is touched.
+ * FILL: covered pixels become colour; for NV12 colour is converted once, on the host, to (Yc, Uc, Vc) with the
+ *   FVP_RGB2YUV_* constants exactly as fvp_draw_poses_nv12 converts a palette entry; covered luma becomes Yc, covered pairs
+ *   (Uc, Vc).  No frame byte is read.
+ * Never read and never written: pitch padding, the bytes between frames, the bytes of other frames' cells.
+ * One workgroup owns a 64 x 32 pixel tile of one frame - whole cells for every permitted cell size.  It reads the frame's
+ * ROIs (at most 64) and leaves if none can cover a pixel of the tile; otherwise: coverage, the touched cells marked in LDS,
+ * barrier, integer sums of the touched cells in LDS (integer adds commute: the result does not depend on scheduling),
+ * barrier, write.  Every read of a cell precedes the barrier and every write follows it, in the one workgroup that owns the
+ * cell: that is what makes in place safe.  An NV12 (U, V) pair is one 2-byte load and one 2-byte store, luma goes byte by
+ * byte.
+ * FVP_EINVAL: null frames (y, uv) or rois; F or R < 0; rois_per_frame < 1; R != F * rois_per_frame; cell not in {2, 4, 8,
+ * 16, 32}; unknown shape or mode; FILL with a null colour; Hs or Ws < 1; NV12: every surface rule of fvp_draw_poses_nv12
+ * (odd Hs or Ws; y_pitch < Ws or uv_pitch < Ws; odd uv address, uv_pitch or uv_frame_stride; unknown standard; with F > 1,
+ * y_frame_stride < (Hs-1) * y_pitch + Ws or uv_frame_stride < (Hs/2-1) * uv_pitch + Ws).  FVP_ELIMIT: rois_per_frame > 64;
+ * Hs or Ws > 16384; F > 65535 (one grid plane per frame).  Nothing is written when an error is returned.  R == 0 (hence
+ * also F == 0) returns 0 without a launch.  Not built: Gaussian blur, rotated boxes, a face detector, I420 / P010 surfaces,
+ * pitched RGB frames. */
+int fvp_anonymise_rois(uint8_t* frames /* [F][Hs][Ws][3], in place */, int F, int Hs, int Ws,
+                       const float* rois /* DEVICE [R][4] */, int R, int rois_per_frame, int cell,
+                       int shape /* FVP_ANON_RECT, _ELLIPSE */, int mode /* FVP_ANON_MOSAIC, _FILL */,
+                       const uint8_t* colour /* HOST [3], R G B */, fvp_stream_t s);
+int fvp_anonymise_rois_nv12(uint8_t* y, uint8_t* uv /* in place */, int F, int Hs, int Ws, long y_pitch, long uv_pitch,
+                            long y_frame_stride, long uv_frame_stride, /* bytes */
+                            int standard /* FVP_YUV_* */, const float* rois /* DEVICE [R][4] */, int R, int rois_per_frame,
+                            int cell, int shape, int mode, const uint8_t* colour /* HOST [3], R G B */, fvp_stream_t s);
 
 /* ---- joint visibility per view (ABI 17): a device-side occlusion test ---------------------------------------------------
  * fvp_joint_evidence says where a joint lands in every view and what the heatmap holds there, not whether the camera can see

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libfvp_hip.so"
-ABI_VERSION = 23          # include/fvp.h FVP_ABI_VERSION
+ABI_VERSION = 24          # include/fvp.h FVP_ABI_VERSION
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 FVP_CAM_FLOATS = 24
@@ -38,6 +38,7 @@ BB_OUT_HEAT = 8
 BB_STEM = 16
 INGEST_SWAP_RB, INGEST_GENERAL = 1, 2
 YUV_BT601_LIMITED, YUV_BT709_LIMITED, YUV_BT601_FULL, YUV_BT709_FULL = 0, 1, 2, 3
+BAYER_RGGB, BAYER_GRBG, BAYER_GBRG, BAYER_BGGR = 0, 1, 2, 3
 ANON_RECT, ANON_ELLIPSE = 0, 1
 ANON_MOSAIC, ANON_FILL = 0, 1
 
@@ -119,6 +120,9 @@ SIGNATURES = {
     "fvp_ingest_frames": [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I, _I, _P, _P, _P],
     "fvp_ingest_nv12": [_P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, C.POINTER(_F), C.POINTER(_F),
                         C.POINTER(_F), _I, _I, _P, _P, _P],
+    "fvp_demosaic_bayer": [_P, _I, _I, _I, C.c_long, C.c_long, _I, _P, _I, _P, _P],
+    "fvp_ingest_bayer": [_P, _I, _I, _I, C.c_long, C.c_long, _I, _P, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _I, _I,
+                         _P, _P, _P],
     "fvp_draw_poses": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_uint8), _I, _I, _I, _I,
                        _F, _P],
     "fvp_draw_poses_nv12": [_P, _P, _I, _I, _I, _I, C.c_long, C.c_long, C.c_long, C.c_long, _I, _P, _P, _P, _I, _I,

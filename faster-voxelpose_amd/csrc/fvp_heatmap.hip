@@ -244,6 +244,264 @@ k_ingest_nv12(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, i
   });
 }
 
+// ---- Bayer raw frames (fvp_demosaic_bayer, fvp_ingest_bayer; include/fvp.h, ABI 24) -------------------------------------
+// One byte per source pixel.  The source RGB pixel is the integer Malvar-He-Cutler filter of include/fvp.h: bayer_px() on
+// the six neighbour sums of a site, the only place the formulas are written.  Three kernels use it:
+//   k_demosaic_bayer       a lane owns 4 x 2 pixels (two whole cells): a 6 x 8 window read as three dwords per row where
+//                          the row is 4-byte aligned (bytes otherwise, row by row), 12-byte stores;
+//   k_ingest_bayer_lds     a workgroup owns 64 x 8 destination pixels: the source rectangle of its taps (from inv at the
+//                          tile's corners: every rounded operation of ingest_coord is monotone, so the extremes are there)
+//                          plus the halo goes into LDS with dword loads, is demosaiced and toned ONCE there by the same
+//                          4 x 2 block code into one packed dword per pixel, and ingest_pair's tap is one LDS read;
+//   k_ingest_bayer_gather  any matrix: 13 byte loads per tap.  Taken when the rectangle of bayer_lds_plan() does not fit.
+// The site type of a pixel depends on its parity alone, the pattern is uniform: no lane diverges on it.
+struct BayerPrm {
+  long pitch, frame;
+  int rx, ry;
+};
+struct BayerRgb { int r, g, b; };
+
+// about the edge sample, without repeating it.  The final clamp never acts on a neighbour of a real pixel (offsets <= 2,
+// n >= 4): it keeps the columns past a frame whose width is no multiple of 4, which nothing uses, inside the row.
+__device__ __forceinline__ int bayer_reflect(int i, int n) {
+  i = i < 0 ? -i : i;
+  i = i >= n ? 2 * (n - 1) - i : i;
+  return i < 0 ? 0 : i;
+}
+
+__device__ __forceinline__ int bayer_round(int x16) {        // clip(0, 255, (X16 + 8) >> 4); >> is arithmetic
+  const int v = (x16 + 8) >> 4;
+  return v < 0 ? 0 : v > 255 ? 255 : v;
+}
+
+// xr: the site's column parity is the red one; yr: its row parity is the red one
+__device__ __forceinline__ BayerRgb bayer_px(int c, int H1, int V1, int D, int H2, int V2, bool xr, bool yr) {
+  const int own = 16 * c;
+  int r, g, b;
+  if (xr == yr) {                                            // a red or a blue site
+    g = 8 * c + 4 * (H1 + V1) - 2 * (H2 + V2);
+    const int third = 12 * c + 4 * D - 3 * (H2 + V2);
+    r = xr ? own : third;
+    b = xr ? third : own;
+  } else {                                                   // a green site; yr: in a red row
+    g = own;
+    const int row = 10 * c + 8 * H1 - 2 * D - 2 * H2 + V2, col = 10 * c + 8 * V1 - 2 * D - 2 * V2 + H2;
+    r = yr ? row : col;
+    b = yr ? col : row;
+  }
+  return BayerRgb{bayer_round(r), bayer_round(g), bayer_round(b)};
+}
+
+// bytes 2..9 of three consecutive dwords: the columns x - 2 .. x + 5 of a block at x, the dwords starting at x - 4
+__device__ __forceinline__ void bayer_unpack(uint32_t d0, uint32_t d1, uint32_t d2, int (&w)[8]) {
+  w[0] = int((d0 >> 16) & 0xffu);
+  w[1] = int(d0 >> 24);
+  w[2] = int(d1 & 0xffu);
+  w[3] = int((d1 >> 8) & 0xffu);
+  w[4] = int((d1 >> 16) & 0xffu);
+  w[5] = int(d1 >> 24);
+  w[6] = int(d2 & 0xffu);
+  w[7] = int((d2 >> 8) & 0xffu);
+}
+
+// The 4 x 2 block at even (x, y) from its window w (rows y - 2 .. y + 3, columns x - 2 .. x + 5) as R | G << 8 | B << 16.
+// tone_l: the table in LDS, read when has_tone (uniform).
+__device__ __forceinline__ void bayer_block(const int (&w)[6][8], int rx, int ry, bool has_tone, const uint8_t* tone_l,
+                                            uint32_t (&out)[2][4]) {
+#pragma unroll
+  for (int py = 0; py < 2; ++py)
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+      const int r = py + 2, q = px + 2;
+      BayerRgb v = bayer_px(w[r][q], w[r][q - 1] + w[r][q + 1], w[r - 1][q] + w[r + 1][q],
+                            w[r - 1][q - 1] + w[r - 1][q + 1] + w[r + 1][q - 1] + w[r + 1][q + 1],
+                            w[r][q - 2] + w[r][q + 2], w[r - 2][q] + w[r + 2][q], (px & 1) == rx, (py & 1) == ry);
+      if (has_tone) {
+        v.r = tone_l[v.r];
+        v.g = tone_l[256 + v.g];
+        v.b = tone_l[512 + v.b];
+      }
+      out[py][px] = uint32_t(v.r) | (uint32_t(v.g) << 8) | (uint32_t(v.b) << 16);
+    }
+}
+
+__device__ __forceinline__ void bayer_stage_tone(const uint8_t* __restrict__ tone, uint8_t* tone_l) {
+  if (tone)                                                  // uniform
+    for (int i = threadIdx.x; i < 768; i += 256) tone_l[i] = tone[i];
+}
+
+struct alignas(4) BayerB12 { uint32_t w[3]; };              // four packed pixels: one 12-byte store
+
+constexpr int kBayerTW = 256, kBayerTH = 8;                  // pixels of a k_demosaic_bayer workgroup: 64 x 4 blocks
+
+__global__ void __launch_bounds__(256)
+k_demosaic_bayer(const uint8_t* __restrict__ raw, int Hs, int Ws, BayerPrm q, const uint8_t* __restrict__ tone,
+                 int tiles_x, int tiles_y, uint8_t* __restrict__ rgb) {
+  __shared__ uint8_t tone_l[768];
+  bayer_stage_tone(tone, tone_l);
+  __syncthreads();
+  const int t = threadIdx.x;
+  const long bid = blockIdx.x;
+  const int tx = int(bid % tiles_x), ty = int((bid / tiles_x) % tiles_y), n = int(bid / (long(tiles_x) * tiles_y));
+  const int x = tx * kBayerTW + (t & 63) * 4, y = ty * kBayerTH + (t >> 6) * 2;
+  if (x >= Ws || y >= Hs) return;
+  const uint8_t* f = raw + long(n) * q.frame;
+  int w[6][8];
+  const bool inner = x >= 4 && x + 8 <= Ws;                  // the three dwords x - 4 .. x + 7 lie inside the row
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const uint8_t* row = f + long(bayer_reflect(y - 2 + r, Hs)) * q.pitch;
+    if (inner && (reinterpret_cast<uintptr_t>(row) & 3) == 0) {
+      const uint32_t* d = reinterpret_cast<const uint32_t*>(row + x - 4);
+      bayer_unpack(d[0], d[1], d[2], w[r]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[r][k] = row[bayer_reflect(x - 2 + k, Ws)];
+    }
+  }
+  uint32_t o[2][4];
+  bayer_block(w, q.rx, q.ry, tone != nullptr, tone_l, o);
+#pragma unroll
+  for (int py = 0; py < 2; ++py) {
+    uint8_t* p = rgb + ((long(n) * Hs + y + py) * Ws + x) * 3;
+    if (x + 4 <= Ws && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+      BayerB12 v;
+      v.w[0] = o[py][0] | (o[py][1] << 24);
+      v.w[1] = (o[py][1] >> 8) | (o[py][2] << 16);
+      v.w[2] = (o[py][2] >> 16) | (o[py][3] << 8);
+      *reinterpret_cast<BayerB12*>(p) = v;
+    } else {
+#pragma unroll
+      for (int px = 0; px < 4; ++px)
+        if (x + px < Ws) {
+          p[3 * px] = uint8_t(o[py][px]);
+          p[3 * px + 1] = uint8_t(o[py][px] >> 8);
+          p[3 * px + 2] = uint8_t(o[py][px] >> 16);
+        }
+    }
+  }
+}
+
+__device__ __forceinline__ IngestPx bayer_unpack_px(uint32_t v) {
+  return IngestPx{{float(v & 0xffu), float((v >> 8) & 0xffu), float((v >> 16) & 0xffu)}};
+}
+
+// Any matrix: a tap demosaics its own pixel from 13 byte loads through L1.
+__global__ void __launch_bounds__(256)
+k_ingest_bayer_gather(const uint8_t* __restrict__ raw, int N, int Hs, int Ws, BayerPrm q, const uint8_t* __restrict__ tone,
+                      IngestPrm p, int H, int W, uint16_t* __restrict__ nhwc8, float* __restrict__ nchw) {
+  __shared__ uint8_t tone_l[768];
+  bayer_stage_tone(tone, tone_l);
+  __syncthreads();
+  const long i = long(blockIdx.x) * 256 + threadIdx.x;       // one thread per pixel PAIR
+  const int w2 = W / 2;
+  if (i >= long(N) * H * w2) return;
+  const int n = int(i / (long(H) * w2));
+  const int r = int(i - long(n) * H * w2);
+  const int y = r / w2, xp = r - y * w2;
+  const uint8_t* f = raw + long(n) * q.frame;
+  const bool has_tone = tone != nullptr;
+  ingest_pair(p, Hs, Ws, H, W, n, y, xp, nhwc8, nchw, [&](int yy, int xx) {
+    const uint8_t* r0 = f + long(yy) * q.pitch;
+    const uint8_t* ra = f + long(bayer_reflect(yy - 1, Hs)) * q.pitch;
+    const uint8_t* rb = f + long(bayer_reflect(yy + 1, Hs)) * q.pitch;
+    const uint8_t* ra2 = f + long(bayer_reflect(yy - 2, Hs)) * q.pitch;
+    const uint8_t* rb2 = f + long(bayer_reflect(yy + 2, Hs)) * q.pitch;
+    const int xa = bayer_reflect(xx - 1, Ws), xb = bayer_reflect(xx + 1, Ws);
+    const int xa2 = bayer_reflect(xx - 2, Ws), xb2 = bayer_reflect(xx + 2, Ws);
+    BayerRgb v = bayer_px(r0[xx], int(r0[xa]) + int(r0[xb]), int(ra[xx]) + int(rb[xx]),
+                          int(ra[xa]) + int(ra[xb]) + int(rb[xa]) + int(rb[xb]), int(r0[xa2]) + int(r0[xb2]),
+                          int(ra2[xx]) + int(rb2[xx]), (xx & 1) == q.rx, (yy & 1) == q.ry);
+    if (has_tone) {
+      v.r = tone_l[v.r];
+      v.g = tone_l[256 + v.g];
+      v.b = tone_l[512 + v.b];
+    }
+    return IngestPx{{float(v.r), float(v.g), float(v.b)}};
+  });
+}
+
+constexpr int kBayerDW = 64, kBayerDH = 8;                   // destination pixels of a k_ingest_bayer_lds workgroup
+
+// LDS: rgb [RH][RW] dwords (R | G << 8 | B << 16 of source pixel (ox + j, oy + i)), then raw [RH + 4][RW + 8] bytes (source
+// rows oy - 2 .., columns ox - 4 .., reflected).  ox is a multiple of 4, oy even, RW a multiple of 4, RH even; RW x RH is
+// bayer_lds_plan()'s bound on every tile's rectangle.
+__global__ void __launch_bounds__(256)
+k_ingest_bayer_lds(const uint8_t* __restrict__ raw, int Hs, int Ws, BayerPrm q, const uint8_t* __restrict__ tone,
+                   IngestPrm p, int H, int W, int tiles_x, int tiles_y, int RW, int RH, uint16_t* __restrict__ nhwc8,
+                   float* __restrict__ nchw) {
+  HIP_DYNAMIC_SHARED(uint32_t, rgbl)
+  __shared__ uint8_t tone_l[768];
+  uint32_t* rawl = rgbl + RH * RW;
+  const int rawd = (RW + 8) / 4;                             // dwords of a raw row in LDS
+  const int t = threadIdx.x;
+  const long bid = blockIdx.x;
+  const int tx = int(bid % tiles_x), ty = int((bid / tiles_x) % tiles_y), n = int(bid / (long(tiles_x) * tiles_y));
+  const int X0 = tx * kBayerDW, Y0 = ty * kBayerDH;
+  const int X1 = X0 + kBayerDW - 1 < W - 1 ? X0 + kBayerDW - 1 : W - 1, Y1 = Y0 + kBayerDH - 1 < H - 1 ? Y0 + kBayerDH - 1 : H - 1;
+  // floor of the source coordinates at the tile's four corners: the extremes over the tile
+  float lox = 0.0f, hix = 0.0f, loy = 0.0f, hiy = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int cx = (k & 1) ? X1 : X0, cy = (k & 2) ? Y1 : Y0;
+    const float fx = floorf(ingest_coord(p.inv[0], p.inv[1], p.inv[2], cx, cy));
+    const float fy = floorf(ingest_coord(p.inv[3], p.inv[4], p.inv[5], cx, cy));
+    lox = k ? fminf(lox, fx) : fx;
+    hix = k ? fmaxf(hix, fx) : fx;
+    loy = k ? fminf(loy, fy) : fy;
+    hiy = k ? fmaxf(hiy, fy) : fy;
+  }
+  // in-frame taps: columns max(lox, 0) .. min(hix + 1, Ws - 1), rows alike; empty when the tile is outside the frame
+  const int x0 = int(fminf(fmaxf(lox, 0.0f), float(Ws))), x1 = int(fminf(fmaxf(hix + 1.0f, -1.0f), float(Ws - 1)));
+  const int y0 = int(fminf(fmaxf(loy, 0.0f), float(Hs))), y1 = int(fminf(fmaxf(hiy + 1.0f, -1.0f), float(Hs - 1)));
+  const int ox = x0 & ~3, oy = y0 & ~1;
+  int rw = 0, rh = 0;
+  if (x1 >= x0 && y1 >= y0) {
+    rw = (x1 + 1 - ox + 3) & ~3;
+    rh = (y1 + 1 - oy + 1) & ~1;
+    rw = rw < RW ? rw : RW;                                  // never acts (bayer_lds_plan); keeps LDS indices inside
+    rh = rh < RH ? rh : RH;
+  }
+  const uint8_t* f = raw + long(n) * q.frame;
+  bayer_stage_tone(tone, tone_l);
+  const int nd = (rw + 8) / 4;
+  for (int i = t; i < (rh + 4) * nd && rw; i += 256) {
+    const int r = i / nd, j = i - r * nd, cx = ox - 4 + 4 * j;
+    const uint8_t* row = f + long(bayer_reflect(oy - 2 + r, Hs)) * q.pitch;
+    uint32_t v;
+    if (cx >= 0 && cx + 4 <= Ws && (reinterpret_cast<uintptr_t>(row) & 3) == 0) {
+      v = *reinterpret_cast<const uint32_t*>(row + cx);
+    } else {
+      v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v |= uint32_t(row[bayer_reflect(cx + k, Ws)]) << (8 * k);
+    }
+    rawl[r * rawd + j] = v;
+  }
+  __syncthreads();
+  const int nbx = rw / 4;
+  for (int i = t; i < nbx * (rh / 2); i += 256) {
+    const int by = i / nbx, bx = i - by * nbx;
+    int w[6][8];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      const uint32_t* d = rawl + (by * 2 + r) * rawd + bx;
+      bayer_unpack(d[0], d[1], d[2], w[r]);
+    }
+    uint32_t o[2][4];
+    bayer_block(w, q.rx, q.ry, tone != nullptr, tone_l, o);
+#pragma unroll
+    for (int py = 0; py < 2; ++py)
+#pragma unroll
+      for (int px = 0; px < 4; ++px) rgbl[(by * 2 + py) * RW + bx * 4 + px] = o[py][px];
+  }
+  __syncthreads();
+  const int xp = X0 / 2 + (t & 31), y = Y0 + (t >> 5);
+  if (2 * xp >= W || y >= H) return;
+  ingest_pair(p, Hs, Ws, H, W, n, y, xp, nhwc8, nchw,
+              [&](int yy, int xx) { return bayer_unpack_px(rgbl[(yy - oy) * RW + (xx - ox)]); });
+}
+
 // ---- poses back onto the camera frames (fvp_draw_poses, include/fvp.h) ---------------------------------------------------
 // Third image kernel of this file, the only one that WRITES frames.  Tile-centric: a workgroup owns 64 x 16 pixels of one
 // frame (a wave's lanes are 64 consecutive x of one row: 192 contiguous bytes), walks the frame's N * (J + L) primitives in
@@ -1088,6 +1346,87 @@ extern "C" int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int H
   FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
   hipLaunchKernelGGL(k_ingest_nv12, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), y, uv, N, Hs, Ws, q,
                      p, H, W, nhwc8, nchw);
+  return launch_status();
+}
+
+// The dispatch rule of fvp_ingest_bayer, a function of inv, H, W, Hs, Ws only: a bound RW x RH on the source rectangle of
+// every 64 x 8 destination tile as k_ingest_bayer_lds lays it out, and whether it fits the LDS budget.  Per axis the taps of
+// a tile span at most floor(|a| (tw - 1) + |b| (th - 1) + 2 err) + 3 pixels: the exact spread, err for the (at most four)
+// fp32 roundings of a coordinate of magnitude <= M, one for the floors, one for the second tap; never more than the frame.
+// The rectangle starts at a multiple of 4 (2 in y) and ends on one: + 3 and rounded up (+ 1 and rounded up).
+constexpr size_t kBayerLdsBytes = 47 * 1024;
+static bool bayer_lds_plan(const float inv[6], int H, int W, int Hs, int Ws, int* RW, int* RH) {
+  int dims[2];
+  const int tw = (W < kBayerDW ? W : kBayerDW) - 1, th = (H < kBayerDH ? H : kBayerDH) - 1;
+  for (int a = 0; a < 2; ++a) {
+    const double ka = std::fabs(double(inv[3 * a])), kb = std::fabs(double(inv[3 * a + 1]));
+    const double M = ka * (W - 1) + kb * (H - 1) + std::fabs(double(inv[3 * a + 2]));
+    const double e = std::floor(ka * tw + kb * th + 2.0 * (5.0 * M * 0x1p-24)) + 3.0;
+    const int n = a ? Hs : Ws;
+    dims[a] = e < double(n) ? int(e) : n;
+  }
+  *RW = (dims[0] + 6) & ~3;
+  *RH = (dims[1] + 2) & ~1;
+  return size_t(*RH) * size_t(*RW) * 4 + size_t(*RH + 4) * size_t(*RW + 8) <= kBayerLdsBytes;
+}
+
+// argument checks both Bayer exports share
+static int bayer_args(const uint8_t* raw, int N, int Hs, int Ws, long pitch, int pattern) {
+  FVP_REQUIRE(raw && N >= 0 && Hs >= 4 && Ws >= 4 && Hs % 2 == 0 && Ws % 2 == 0 && pitch >= Ws);
+  FVP_REQUIRE(pattern >= FVP_BAYER_RGGB && pattern <= FVP_BAYER_BGGR);
+  return 0;
+}
+
+extern "C" int fvp_demosaic_bayer(const uint8_t* raw, int N, int Hs, int Ws, long pitch, long frame_stride, int pattern,
+                                  const uint8_t* tone, int flags, uint8_t* rgb, fvp_stream_t s) {
+  if (int rc = bayer_args(raw, N, Hs, Ws, pitch, pattern)) return rc;
+  FVP_REQUIRE(rgb && flags == 0);
+  if (N == 0) return 0;
+  FVP_LIMIT(Hs <= 16384 && Ws <= 16384);
+  const int tiles_x = ceil_div(Ws, kBayerTW), tiles_y = ceil_div(Hs, kBayerTH);
+  const long blocks = long(tiles_x) * tiles_y * N;
+  FVP_LIMIT(blocks < (1l << 31));
+  const BayerPrm q = {pitch, frame_stride, pattern & 1, pattern >> 1};
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  hipLaunchKernelGGL(k_demosaic_bayer, dim3(unsigned(blocks)), dim3(256), 0, as_stream(s), raw, Hs, Ws, q, tone, tiles_x,
+                     tiles_y, rgb);
+  return launch_status();
+}
+
+extern "C" int fvp_ingest_bayer(const uint8_t* raw, int N, int Hs, int Ws, long pitch, long frame_stride, int pattern,
+                                const uint8_t* tone, const float inv[6], const float mean[3], const float stdv[3], int H,
+                                int W, uint16_t* nhwc8, float* nchw, fvp_stream_t s) {
+  if (int rc = bayer_args(raw, N, Hs, Ws, pitch, pattern)) return rc;
+  FVP_REQUIRE(inv && mean && stdv && (nhwc8 || nchw) && H > 0 && W > 0 && W % 2 == 0);
+  IngestPrm p;
+  for (int i = 0; i < 6; ++i) {
+    FVP_REQUIRE(std::isfinite(inv[i]));
+    p.inv[i] = inv[i];
+  }
+  for (int c = 0; c < 3; ++c) {
+    FVP_REQUIRE(std::isfinite(mean[c]) && std::isfinite(stdv[c]) && stdv[c] != 0.0f);
+    p.mean[c] = mean[c];
+    p.stdv[c] = stdv[c];
+  }
+  if (N == 0) return 0;
+  FVP_LIMIT(Hs < (1 << 24) && Ws < (1 << 24) && H < (1 << 24) && W < (1 << 24));   // pixel indices exact in fp32
+  const BayerPrm q = {pitch, frame_stride, pattern & 1, pattern >> 1};
+  const long pairs = long(N) * H * (W / 2);
+  FVP_LIMIT((pairs + 255) / 256 < (1l << 31));
+  int RW = 0, RH = 0;
+  const bool staged = bayer_lds_plan(p.inv, H, W, Hs, Ws, &RW, &RH);
+  const int tiles_x = ceil_div(W, kBayerDW), tiles_y = ceil_div(H, kBayerDH);
+  const long blocks = long(tiles_x) * tiles_y * N;
+  FVP_LIMIT(!staged || blocks < (1l << 31));
+  ProfScope ps(FVP_K_OTHER, as_stream(s));
+  if (staged) {
+    const size_t lds = size_t(RH) * RW * 4 + size_t(RH + 4) * (RW + 8);
+    hipLaunchKernelGGL(k_ingest_bayer_lds, dim3(unsigned(blocks)), dim3(256), lds, as_stream(s), raw, Hs, Ws, q, tone, p, H,
+                       W, tiles_x, tiles_y, RW, RH, nhwc8, nchw);
+  } else {
+    hipLaunchKernelGGL(k_ingest_bayer_gather, dim3(unsigned((pairs + 255) / 256)), dim3(256), 0, as_stream(s), raw, N, Hs,
+                       Ws, q, tone, p, H, W, nhwc8, nchw);
+  }
   return launch_status();
 }
 

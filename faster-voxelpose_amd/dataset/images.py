@@ -13,6 +13,11 @@ NV12 surfaces - what a hardware decoder or a capture card leaves in device memor
 between: ``Nv12Frames`` describes the two planes (pitch and frame stride are the tensors' strides), ``ingest_nv12`` /
 ``launch_nv12`` call ``fvp_ingest_nv12``, whose outputs equal ``fvp_ingest_frames`` on the frame converted pixel by
 pixel with the integer formula of ``include/fvp.h``.
+
+Bayer raw frames - the 8-bit mosaic a machine-vision camera delivers, one byte per pixel - are the third input:
+``BayerFrames`` describes them, ``ingest_bayer`` / ``launch_bayer`` call ``fvp_ingest_bayer`` (no RGB frame in between),
+``demosaic_bayer`` / ``BayerFrames.to_rgb`` call ``fvp_demosaic_bayer`` for the stages that work on an RGB frame.  The
+outputs of the first equal ``fvp_ingest_frames`` on the output of the second, bit for bit.
 """
 import ctypes as C
 import math
@@ -204,3 +209,107 @@ def ingest_nv12(frames, resize_transform, image_size, mean=IMAGENET_MEAN, std=IM
     out = _out_arg(out, (frames.N, 3, H, W), frames.device)
     launch_nv12(lib, frames, resize_transform, (W, H), mean, std, None, out)
     return out.view(*frames.lead, 3, H, W)
+
+
+BAYER_PATTERNS = {"rggb": capi.BAYER_RGGB, "grbg": capi.BAYER_GRBG, "gbrg": capi.BAYER_GBRG, "bggr": capi.BAYER_BGGR}
+
+
+class BayerFrames:
+    """8-bit Bayer raw camera frames in device memory (no copy):
+
+    ``raw``  uint8 ``[..., Hs, Ws]``, Hs and Ws even and >= 4.  The last dimension is dense, the row stride is the pitch
+    (any value >= Ws, odd ones included) and the leading dimensions flatten to one constant frame stride.  ``pattern``:
+    the 2 x 2 cell at the top-left corner, ``"rggb"`` (BayerRG8), ``"grbg"`` (GR8), ``"gbrg"`` (GB8) or ``"bggr"`` (BG8).
+    ``tone``: uint8 ``[3,256]`` on the frames' device, applied per channel after the demosaic (``tone_table``), or None."""
+
+    def __init__(self, raw, pattern="rggb", tone=None):
+        key = str(pattern).lower()
+        if key not in BAYER_PATTERNS:
+            raise capi.FvpError(f"unknown Bayer pattern {pattern!r} (rggb, grbg, gbrg or bggr)")
+        if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() < 2:
+            raise capi.FvpError("raw must be a uint8 tensor [...,Hs,Ws]")
+        Hs, Ws = int(raw.shape[-2]), int(raw.shape[-1])
+        if Hs < 4 or Ws < 4 or Hs % 2 or Ws % 2:
+            raise capi.FvpError(f"Bayer frames have even height and width of at least 4, got {Hs} x {Ws}")
+        if raw.stride(-1) != 1 or raw.stride(-2) < Ws:
+            raise capi.FvpError("the last dimension of raw must be dense and its rows must not overlap (a row is Ws bytes "
+                                "in a row, only the pitch between rows is free)")
+        if tone is not None:
+            if not isinstance(tone, torch.Tensor) or tone.dtype != torch.uint8 or tuple(tone.shape) != (3, 256) \
+                    or not tone.is_contiguous():
+                raise capi.FvpError("tone must be a contiguous uint8 tensor [3,256]")
+            if tone.device != raw.device:
+                raise capi.FvpError(f"tone is on {tone.device}, the frames are on {raw.device}")
+        self.raw, self.pattern, self.tone = raw, BAYER_PATTERNS[key], tone
+        self.lead = tuple(raw.shape[:-2])
+        self.N = 1
+        for n in self.lead:
+            self.N *= int(n)
+        self.Hs, self.Ws, self.pitch = Hs, Ws, int(raw.stride(-2))
+        fs = _frame_stride(raw, len(self.lead), "raw")
+        self.frame_stride = int(fs) if fs is not None else Hs * self.pitch
+        self.device, self.is_cuda = raw.device, raw.is_cuda
+
+    @staticmethod
+    def tone_table(gains=(1.0, 1.0, 1.0), gamma=1.0, black=0, device=None):
+        """uint8 ``[3,256]``: black level, white-balance gains (R, G, B) and gamma in one table, in float64:
+        ``lut[c][v] = clip(rint(255 * clip((v - black) * gains[c] / (255 - black), 0, 1) ** (1 / gamma)), 0, 255)``."""
+        if not 0 <= float(black) < 255 or not float(gamma) > 0 or len(gains) != 3:
+            raise capi.FvpError("tone_table: 0 <= black < 255, gamma > 0 and three gains")
+        v = np.arange(256, dtype=np.float64)
+        lut = np.empty((3, 256), np.float64)
+        for c in range(3):
+            lin = np.clip((v - float(black)) * float(gains[c]) / (255.0 - float(black)), 0.0, 1.0)
+            lut[c] = np.clip(np.rint(255.0 * lin ** (1.0 / float(gamma))), 0, 255)
+        return torch.from_numpy(lut.astype(np.uint8)).to(device if device is not None else "cpu")
+
+    def to_rgb(self, out=None, _lib=None):
+        """The demosaiced frames, uint8 ``[...,Hs,Ws,3]`` in R, G, B order (``demosaic_bayer``)."""
+        return demosaic_bayer(self, out=out, _lib=_lib)
+
+
+def _bayer_arg(frames):
+    if not isinstance(frames, BayerFrames):
+        raise capi.FvpError(f"frames must be BayerFrames, got {type(frames).__name__}")
+
+
+def launch_bayer(lib, frames, resize_transform, image_size, mean, std, nhwc8, nchw):
+    """One ``fvp_ingest_bayer`` call on the current stream: the Bayer counterpart of ``launch`` (same cached inverse)."""
+    _bayer_arg(frames)
+    W, H = int(image_size[0]), int(image_size[1])
+    inv = _inverse.get(resize_transform)
+    rc = lib.fvp_ingest_bayer(ptr(frames.raw), frames.N, frames.Hs, frames.Ws, frames.pitch, frames.frame_stride,
+                              frames.pattern, ptr(frames.tone), (C.c_float * 6)(*[float(v) for v in inv]), f3(mean), f3(std),
+                              H, W, ptr(nhwc8), ptr(nchw), stream_ptr(frames.device))
+    capi.check(lib, rc, "fvp_ingest_bayer")
+
+
+def ingest_bayer(frames, resize_transform, image_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, _lib=None):
+    """``frames``: ``BayerFrames`` on the GPU with leading dimensions ``[...]``; ``resize_transform`` and ``image_size``
+    as for ``ingest_frames``.  Returns fp32 ``[...,3,H,W]``, RGB order: bit for bit what ``ingest_frames(...,
+    swap_rb=False)`` returns for ``demosaic_bayer(frames)``."""
+    _bayer_arg(frames)
+    require_gpu("ingest_bayer", frames.device, _lib is not None)
+    lib, _ = load_lib(_lib)
+    W, H = int(image_size[0]), int(image_size[1])
+    out = _out_arg(out, (frames.N, 3, H, W), frames.device)
+    launch_bayer(lib, frames, resize_transform, (W, H), mean, std, None, out)
+    return out.view(*frames.lead, 3, H, W)
+
+
+def demosaic_bayer(frames, out=None, _lib=None):
+    """``frames``: ``BayerFrames`` on the GPU -> uint8 ``[...,Hs,Ws,3]`` in R, G, B order (one ``fvp_demosaic_bayer`` call
+    on the current stream): the frames overlay, crops, re-ID and anonymiser take.  ``out``: a contiguous uint8 tensor of
+    that many elements to write into."""
+    _bayer_arg(frames)
+    require_gpu("demosaic_bayer", frames.device, _lib is not None)
+    lib, _ = load_lib(_lib)
+    shape = (*frames.lead, frames.Hs, frames.Ws, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or out.numel() != math.prod(shape) or not out.is_contiguous() or out.device != frames.device:
+        raise capi.FvpError(f"out must be a contiguous uint8 tensor of {shape} on {frames.device}")
+    rc = lib.fvp_demosaic_bayer(ptr(frames.raw), frames.N, frames.Hs, frames.Ws, frames.pitch, frames.frame_stride,
+                                frames.pattern, ptr(frames.tone), 0, ptr(out), stream_ptr(frames.device))
+    capi.check(lib, rc, "fvp_demosaic_bayer")
+    return out.view(shape)

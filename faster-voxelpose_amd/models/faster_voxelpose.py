@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import _capi as capi
-from ..dataset.images import Nv12Frames, ingest_frames, ingest_nv12
+from ..dataset.images import BayerFrames, Nv12Frames, demosaic_bayer, ingest_bayer, ingest_frames, ingest_nv12
 from ..engine import HotPath
 from .human_detection_net import HumanDetectionNet
 from .joint_localization_net import JointLocalizationNet
@@ -89,7 +89,9 @@ _CHECKED_FIRST = ("smoother", "visibility", "overlay", "crops")    # forward() c
 _REMEDY = {"tracker": "set model.tracker (a PoseTracker) too", "evidence": "set model.evidence = True too",
            "triangulator": "set model.triangulator = JointTriangulator(cfg) as well",
            "frames": "pass them as views, uint8 [B,V,Hs,Ws,3] or Nv12Frames (float images and input_heatmaps alone leave "
-                     "nothing to work on; an overlay takes Nv12Frames only when built with nv12=True)"}
+                     "nothing to work on; an overlay takes Nv12Frames only when built with nv12=True)",
+           "bayer_rgb": "set model.bayer_rgb = True (BayerFrames views hold no RGB frame: with it the forward demosaics "
+                        "them once into model.last_frames, uint8 [B,V,Hs,Ws,3] in R, G, B order, and works on that)"}
 
 
 class FasterVoxelPoseNet(nn.Module):
@@ -110,6 +112,12 @@ class FasterVoxelPoseNet(nn.Module):
         # `last_evidence`; the returned tuple is the same either way
         self.evidence = False
         self.last_evidence = None
+        # BayerFrames views (dataset/images.py).  False: fvp_ingest_bayer feeds the backbone and no RGB frame exists, so a
+        # stage that needs frames is refused.  True: the forward demosaics once into `last_frames` (uint8 [B,V,Hs,Ws,3], R, G,
+        # B), ingests that - the same bits - and hands it to overlay and crops; PersonReId, LimbModel and FaceAnonymiser take
+        # it from there
+        self.bayer_rgb = False
+        self.last_frames = None
         for stage in STAGES:                             # every optional stage unset (STAGES says what each does when set)
             setattr(self, stage.attr, None)
             if stage.last is not None:
@@ -138,6 +146,10 @@ class FasterVoxelPoseNet(nn.Module):
                 ok = self.evidence
             elif need == "frames":
                 # an NV12 surface is the decoder's own memory: drawn on only by an overlay built with nv12=True
+                if isinstance(views, BayerFrames):        # a sensor's mosaic: the stage works on the demosaiced frames
+                    if not self.bayer_rgb:
+                        raise capi.FvpError(f"model.{stage.attr} {why}: {_REMEDY['bayer_rgb']}")
+                    continue
                 ok = getattr(getattr(self, stage.attr), "nv12", True) if isinstance(views, Nv12Frames) \
                     else torch.is_tensor(views) and views.dtype == torch.uint8
             else:
@@ -145,16 +157,20 @@ class FasterVoxelPoseNet(nn.Module):
             if not ok:
                 raise capi.FvpError(f"model.{stage.attr} {why}: {_REMEDY[need]}")
 
-    def _heatmaps_from_views(self, backbone, views, resize_transform):
-        """``views`` - fp32 images [B,V,3,H,W], uint8 camera frames [B,V,Hs,Ws,3] or an ``Nv12Frames`` with leading
-        dimensions [B,V] (dataset/images.py) - through ``backbone`` -> ``input_heatmaps`` [B,V,J,H/4,W/4]."""
+    def _heatmaps_from_views(self, backbone, views, resize_transform, swap_rb=None):
+        """``views`` - fp32 images [B,V,3,H,W], uint8 camera frames [B,V,Hs,Ws,3] (BGR unless ``swap_rb`` is False), or an
+        ``Nv12Frames`` / ``BayerFrames`` with leading dimensions [B,V] (dataset/images.py) - through ``backbone`` ->
+        ``input_heatmaps`` [B,V,J,H/4,W/4]."""
         nv12 = isinstance(views, Nv12Frames)              # a decoder's NV12 surface
-        frames = not nv12 and views.dtype == torch.uint8  # raw camera frames
+        bayer = isinstance(views, BayerFrames)            # a sensor's Bayer mosaic (model.bayer_rgb False: no RGB frame)
+        frames = not (nv12 or bayer) and views.dtype == torch.uint8  # raw camera frames
         if nv12:
             if len(views.lead) != 2:
                 raise capi.FvpError(f"NV12 views must have leading dimensions [B,V], got {views.lead}")
             if resize_transform is None:
                 raise capi.FvpError("NV12 views need resize_transform (camera -> network pixels) to be resized")
+            B, V = views.lead
+        elif bayer:
             B, V = views.lead
         else:
             if frames:
@@ -167,8 +183,11 @@ class FasterVoxelPoseNet(nn.Module):
             # bf16 HIP backbone (models/resnet.py): all B*V views in one pass - frames and surfaces through the ingest kernel
             # straight into its bf16 input, no RGB frame and no fp32 image in between; it writes the heatmaps as NCHW
             # (returned, like the reference) and in the channels-last layout the projection reads
-            nchw, cl = backbone._run(views if nv12 else views.flatten(0, 1), True, True,
-                                     resize_transform=resize_transform if nv12 or frames else None)
+            if frames and swap_rb is not None:
+                nchw, cl = backbone._run(views.flatten(0, 1), True, True, resize_transform=resize_transform, swap_rb=swap_rb)
+            else:
+                nchw, cl = backbone._run(views if nv12 or bayer else views.flatten(0, 1), True, True,
+                                         resize_transform=resize_transform if nv12 or bayer or frames else None)
             input_heatmaps = nchw.view(B, V, *nchw.shape[1:])
             if cl.shape[-1] == self.engine.JP:
                 self.engine.adopt_staging(input_heatmaps, cl)
@@ -176,8 +195,11 @@ class FasterVoxelPoseNet(nn.Module):
         # any torch module: the fp32 tensor the reference's loader would have produced, then per-view passes (:36-38)
         if nv12:
             views = ingest_nv12(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+        elif bayer:
+            views = ingest_bayer(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
         elif frames:
-            views = ingest_frames(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, _lib=self.engine.lib)
+            views = ingest_frames(views, resize_transform, self.cfg.DATASET.IMAGE_SIZE, swap_rb=swap_rb is None or swap_rb,
+                                  _lib=self.engine.lib)
         return torch.stack([backbone(views[:, c]) for c in range(V)], dim=1)
 
     def forward(self, backbone=None, views=None, meta=None, targets=None, input_heatmaps=None, cameras=None,
@@ -188,7 +210,17 @@ class FasterVoxelPoseNet(nn.Module):
         for attr in _CHECKED_FIRST:
             if getattr(self, attr) is not None:
                 self._check_needs(_STAGE[attr], views)
-        if views is not None:
+        if isinstance(views, BayerFrames):
+            if len(views.lead) != 2:
+                raise capi.FvpError(f"Bayer views must have leading dimensions [B,V], got {views.lead}")
+            if resize_transform is None:
+                raise capi.FvpError("Bayer views need resize_transform (camera -> network pixels) to be resized")
+        if isinstance(views, BayerFrames) and self.bayer_rgb:
+            # one demosaic into last_frames; from here on the views ARE that RGB frame (include/fvp.h: ingesting it gives the
+            # bits fvp_ingest_bayer gives), for the ingest and for overlay and crops
+            views = self.last_frames = demosaic_bayer(views, _lib=self.engine.lib)
+            input_heatmaps = self._heatmaps_from_views(backbone, views, resize_transform, swap_rb=False)
+        elif views is not None:
             input_heatmaps = self._heatmaps_from_views(backbone, views, resize_transform)
         _, _, proposal_centers, _ = self.pose_net(input_heatmaps, meta, cameras, resize_transform)
         mask = self.engine.last["valid"]              # uint8 [B,N] = proposal_centers[:, :, 3] >= 0 (:45), written by fvp_proposals

@@ -8,7 +8,8 @@ interpreter ``fvp_bb_run`` (NHWC bf16 activations, implicit-GEMM convs on
 epilogue together with the residual add and ReLU).  ``forward_channels_last`` returns the fp32
 heatmaps directly in the ``[N, H*W, JP]`` staging layout the projection kernels read.  ``forward_frames`` takes raw
 uint8 camera frames - packed BGR / RGB, or an NV12 surface as ``Nv12Frames`` - instead of the normalised fp32 image:
-``fvp_ingest_frames`` / ``fvp_ingest_nv12`` (dataset/images.py) write the bf16 input buffer directly.
+``fvp_ingest_frames`` / ``fvp_ingest_nv12`` / ``fvp_ingest_bayer`` (a sensor's mosaic as ``BayerFrames``; dataset/images.py)
+write the bf16 input buffer directly.
 """
 import ctypes as C
 import os
@@ -212,19 +213,23 @@ class PoseResNet(ParamTree):
     # ---- forward ----------------------------------------------------------------------------------------------------
     def _run(self, x, want_cl, want_nchw, resize_transform=None, swap_rb=None):
         """``x``: fp32 images [N,3,H,W], or uint8 camera frames [N,Hs,Ws,3] (``swap_rb`` None = True: BGR) or
-        ``Nv12Frames`` (any leading dimensions, flattened to N; no ``swap_rb``) together with ``resize_transform``."""
+        ``Nv12Frames`` / ``BayerFrames`` (any leading dimensions, flattened to N; no ``swap_rb``) together with
+        ``resize_transform``."""
         nv12 = isinstance(x, IMG.Nv12Frames)
-        frames = nv12 or x.dtype == torch.uint8
+        bayer = isinstance(x, IMG.BayerFrames)
+        frames = nv12 or bayer or x.dtype == torch.uint8
         if frames:
             if nv12 and swap_rb is not None:
                 raise capi.FvpError("swap_rb has no meaning for NV12 frames (the conversion writes R, G, B)")
-            if not nv12 and (x.dim() != 4 or x.shape[-1] != 3):
+            if bayer and swap_rb is not None:
+                raise capi.FvpError("swap_rb has no meaning for Bayer frames (the demosaic writes R, G, B)")
+            if not (nv12 or bayer) and (x.dim() != 4 or x.shape[-1] != 3):
                 raise capi.FvpError(f"uint8 frames must be [N,Hs,Ws,3] (HWC), got {tuple(x.shape)}")
             if resize_transform is None:
                 raise capi.FvpError("camera frames need resize_transform (camera -> network pixels)")
             if self.image_size is None:
                 raise capi.FvpError("camera frames need cfg.DATASET.IMAGE_SIZE")
-            N, (W, H) = (x.N if nv12 else x.shape[0]), self.image_size
+            N, (W, H) = (x.N if nv12 or bayer else x.shape[0]), self.image_size
         else:
             assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
             N, _, H, W = x.shape
@@ -244,6 +249,8 @@ class PoseResNet(ParamTree):
         bufs[0] = torch.empty((N, h, w // 2, c), dtype=torch.bfloat16, device=dev)
         if nv12:                     # colour conversion + warp + normalise + bf16 in one kernel, from the decoder's surface
             IMG.launch_nv12(self.lib, x, resize_transform, (W, H), IMG.IMAGENET_MEAN, IMG.IMAGENET_STD, bufs[0], None)
+        elif bayer:                  # demosaic + tone + warp + normalise + bf16 in one kernel, from the sensor's mosaic
+            IMG.launch_bayer(self.lib, x, resize_transform, (W, H), IMG.IMAGENET_MEAN, IMG.IMAGENET_STD, bufs[0], None)
         elif frames:                 # warp + swap + normalise + bf16 in one kernel: no fp32 image tensor exists
             IMG.launch(self.lib, x.contiguous(), resize_transform, (W, H), swap_rb is None or bool(swap_rb), IMG.IMAGENET_MEAN,
                        IMG.IMAGENET_STD, bufs[0], None)
@@ -287,7 +294,7 @@ class PoseResNet(ParamTree):
 
     def forward_frames(self, frames, resize_transform, swap_rb=None):
         """uint8 camera frames [N,Hs,Ws,3] (HWC, native resolution; BGR unless ``swap_rb=False``) or ``Nv12Frames``
-        (a decoder's surface; ``swap_rb`` must stay None) -> [N,J,H/4,W/4] fp32 heatmaps at cfg.DATASET.IMAGE_SIZE: the
+        (a decoder's surface; ``swap_rb`` must stay None) or ``BayerFrames`` (a sensor's mosaic; likewise) -> [N,J,H/4,W/4] fp32 heatmaps at cfg.DATASET.IMAGE_SIZE: the
         reference's offline warpAffine + loader transform + backbone.  ``resize_transform`` is the forward 2x3 of
         ``get_resize_transform``."""
         return self._run(frames, False, True, resize_transform=resize_transform, swap_rb=swap_rb)[0]

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FVP_ABI_VERSION 23
+#define FVP_ABI_VERSION 24
 #define FVP_MAX_VIEWS 8
 #define FVP_CAM_FLOATS 24 /* R[9] T[3] fx fy cx cy k[3] p[2] + 3 pad */
 #define FVP_MAX_JOINTS 32
@@ -701,6 +701,58 @@ int fvp_ingest_nv12(const uint8_t* y, const uint8_t* uv, int N, int Hs, int Ws, 
                     long y_frame_stride, long uv_frame_stride, /* bytes */
                     int standard, const float inv[6], const float mean[3], const float stdv[3], int H, int W,
                     uint16_t* nhwc8, float* nchw, fvp_stream_t s);
+
+/* ---- Bayer raw camera frames (ABI 24): fvp_demosaic_bayer, fvp_ingest_bayer ---------------------------------------------
+ * What a machine-vision camera delivers: the sensor's 8-bit Bayer mosaic (BayerRG8 / GR8 / GB8 / BG8), one byte per pixel.
+ * fvp_ingest_bayer takes it to the backbone input in one pass, with no RGB frame in between; fvp_demosaic_bayer writes the
+ * RGB frame for the stages that work on one.  Everything up to the source RGB pixel is exact integer arithmetic; no
+ * bit-compatibility with any library's demosaic is claimed.
+ * Frame: raw is a DEVICE pointer to N frames of Hs rows of Ws bytes, Hs and Ws both even and >= 4, pitch >= Ws bytes from
+ * row to row, frame_stride bytes from frame to frame.  Pitch, stride and the address may be odd: no alignment is required.
+ * pattern names the 2 x 2 cell at the frame's top-left corner by where its red sample (rx, ry) lies:
+ *   FVP_BAYER_RGGB 0: (0, 0)    FVP_BAYER_GRBG 1: (1, 0)    FVP_BAYER_GBRG 2: (0, 1)    FVP_BAYER_BGGR 3: (1, 1)
+ * The site (x, y) is red if (x&1) == rx and (y&1) == ry, blue if both differ, green otherwise; a green site is "in a red
+ * row" if (y&1) == ry, else "in a blue row".
+ * Border: a neighbour index outside the frame is reflected about the edge sample without repeating it (i < 0 -> -i,
+ * i >= n -> 2(n-1) - i).  Offsets are at most 2 and n >= 4, so the result is inside; reflection keeps the parity, so a
+ * reflected neighbour has the colour the formula expects.
+ * Neighbour sums at (x, y), int32, raw(dy, dx) the reflected neighbour:
+ *   c  = raw(0,0)               H1 = raw(0,-1) + raw(0,1)      V1 = raw(-1,0) + raw(1,0)
+ *   D  = raw(-1,-1) + raw(-1,1) + raw(1,-1) + raw(1,1)         H2 = raw(0,-2) + raw(0,2)      V2 = raw(-2,0) + raw(2,0)
+ * Sixteenths of the three colours - the Malvar-He-Cutler 5 x 5 linear filter with its coefficients doubled so that all are
+ * integers; "third colour" is the non-green colour the site does not carry:
+ *   the site's own colour                                          16c
+ *   green at a red or blue site                                    8c + 4(H1 + V1) - 2(H2 + V2)
+ *   the third colour at a red or blue site                         12c + 4D - 3(H2 + V2)
+ *   at a green site, the colour of its row neighbours
+ *   (red in a red row, blue in a blue row)                         10c + 8 H1 - 2D - 2 H2 + V2
+ *   at a green site, the colour of its column neighbours           10c + 8 V1 - 2D - 2 V2 + H2
+ * value = clip(0, 255, (X16 + 8) >> 4), >> arithmetic; every X16 lies in [-3060, 7140].
+ * tone: a DEVICE pointer to uint8 [3][256], or NULL (the identity).  After the clip R = tone[0][R], G = tone[1][G],
+ * B = tone[2][B]: one table carries black level, white-balance gains and gamma for sensors that deliver linear data.
+ * The triple is the SOURCE RGB PIXEL at integer (xi, yi).
+ * fvp_demosaic_bayer writes every source RGB pixel to rgb [N][Hs][Ws][3] in R, G, B order: the contiguous HWC layout that
+ * fvp_ingest_frames, fvp_draw_poses, fvp_crop_rois, fvp_person_signature and fvp_anonymise_rois take.  flags must be 0.
+ * fvp_ingest_bayer: from the source RGB pixel on, the arithmetic is exactly that of fvp_ingest_frames with flags = 0 (output
+ * channel 0 is R): coordinates through inv, floor, four taps with a zero border (a tap outside [0,Ws) x [0,Hs) is 0 and is
+ * not demosaiced), the same fp32 bilinear expression, / 255, - mean, / stdv, bf16 round-to-nearest-even.  Hence:
+ * THE OUTPUTS OF fvp_ingest_bayer EQUAL, BIT FOR BIT, fvp_ingest_frames (flags = 0) APPLIED TO THE OUTPUT OF
+ * fvp_demosaic_bayer.  inv, mean, stdv: HOST memory, by value; nhwc8 / nchw as for fvp_ingest_frames (either may be NULL).
+ * Which of its two kernels runs (the source rectangle of a 64 x 8 destination tile demosaiced once in LDS, or a gather that
+ * demosaics per tap when that rectangle does not fit) is a function of inv, H, W, Hs, Ws only and changes no bit.
+ * FVP_EINVAL: a null raw, inv, mean or stdv; a null rgb (demosaic); both outputs null (ingest); N < 0; Hs or Ws odd or < 4;
+ * pitch < Ws; pattern outside 0..3; non-zero flags; odd W, or H or W < 1; non-finite inv, mean or stdv, or stdv == 0.
+ * FVP_ELIMIT: the ingest as fvp_ingest_frames; the demosaic Hs or Ws > 16384, or a grid of 2^31 or more workgroups (one per
+ * 256 x 8 pixels).  Nothing is written when an error is returned.  N == 0 returns 0 without a launch.
+ * Not built: 10-, 12- or 16-bit and packed raw formats; gains applied to the mosaic before interpolation (the tone table
+ * acts after it); edge-directed demosaics; a pitched RGB output; Bayer input for the overlay, the crops or the anonymiser
+ * directly - they take the demosaiced frame. */
+enum { FVP_BAYER_RGGB = 0, FVP_BAYER_GRBG = 1, FVP_BAYER_GBRG = 2, FVP_BAYER_BGGR = 3 };
+int fvp_demosaic_bayer(const uint8_t* raw, int N, int Hs, int Ws, long pitch, long frame_stride, /* bytes */
+                       int pattern, const uint8_t* tone, int flags, uint8_t* rgb /* [N][Hs][Ws][3] */, fvp_stream_t s);
+int fvp_ingest_bayer(const uint8_t* raw, int N, int Hs, int Ws, long pitch, long frame_stride, /* bytes */
+                     int pattern, const uint8_t* tone, const float inv[6], const float mean[3], const float stdv[3], int H,
+                     int W, uint16_t* nhwc8, float* nchw, fvp_stream_t s);
 
 /* ---- skeleton overlay (ABI 14): the poses drawn onto the camera frames they were computed from ------------------------
  * Counterpart of the reference's host-side lib/utils/vis.py::save_image_with_poses (cv2.circle / cv2.line per view), on the
